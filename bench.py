@@ -13,9 +13,15 @@ every rank, so each timed step ends with the all_reduce(SUM) of its gradient ove
 section 8e; also timed on its own as allreduce_ms).  The timed region is bracketed by barriers and
 the max over ranks is reported.  Under torchrun the ranks come from its environment; `bench.py --gpus N` started without
 a launcher spawns the N rank processes itself (before any GPU call) and exits with their status.
-The launched world size must equal --gpus (exit status 2 otherwise).  With N > 1 the rank images
-are then all-gathered over RCCL (BASELINE cfg4: 512 items on 8 GPUs "with RCCL gather") and that
-time is reported separately as gather_ms.
+The launched world size must equal --gpus (exit status 2 otherwise).
+
+A plain run sets up, runs --warmup steps, times --steps steps, writes the last timed step's outputs
+when --dump-outputs DIR is given, and prints the result line with the headline figure.  --full adds,
+after that, everything else the bench measures (full_measurements): the host's enqueue times, the
+per-kernel times and the dominant kernel's roofline, the copy ceiling, the rocprofv3 --pmc passes,
+the forward's face-test rate, the CPU baseline, --graph-steps, and with N > 1 the all_reduce timed
+on its own and the all_gather of the rank images over RCCL (BASELINE cfg4: 512 items on 8 GPUs "with
+RCCL gather", reported separately as gather_ms).  The --no-* options and --cpu-seconds trim --full.
 
 Output: one JSON line on rank 0 (see README/DESIGN for field meanings).
 """
@@ -45,13 +51,21 @@ def parse():
     p.add_argument("--image-size", type=int, default=256)
     p.add_argument("--level", type=int, default=4, help="ico-sphere subdivision level (4 -> 5120 faces)")
     p.add_argument("--mode", choices=["rgbsd", "sil"], default="rgbsd")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps, also measure everything beside the headline figure: the host "
+                        "enqueue times, per-kernel times and roofline, copy ceiling, PMC passes, face-test rate, "
+                        "CPU baseline and, with N > 1, the all_reduce and all_gather times (a plain run only "
+                        "warms up, times the steps and prints the result line)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (images, grad_vertices, "
+                        "grad_textures) as DIR/<name>.npy in float32")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=30.0,
                    help="cap on the CPU baseline's timed work (it times the whole batch when that fits)")
     p.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                    help="gloo: rehearse the N > 1 path with ranks sharing GPUs (not for reported numbers)")
     p.add_argument("--graph-steps", type=int, default=0,
-                   help="after the eager timing, time this many replays of the step captured in a HIP graph (0: skip)")
+                   help="with --full: after the eager timing, time this many replays of the step captured in a HIP graph (0: skip)")
     p.add_argument("--no-gather", action="store_true",
                    help="with N > 1, skip the RCCL all_gather of the images timed after the steps (cfg4)")
     p.add_argument("--no-pmc", action="store_true",
@@ -480,6 +494,38 @@ def pmc_child(args):
     torch.cuda.synchronize()
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # all files of one --dump-outputs run together (the limit is 64 MB)
+DUMP_SHARES = (("images", 0.8), ("grad_vertices", 0.1), ("grad_textures", 0.1))
+
+
+def dump_sample(t, budget_bytes, seed):
+    """t as a float32 numpy array when it fits into budget_bytes; otherwise a fixed sample of it: the
+    elements of the flattened array at budget_bytes / 4 sorted indices drawn without replacement by
+    RandomState(seed), which depend on t's shape alone, so two builds dump the same elements."""
+    a = t.detach().to(torch.float32).cpu().numpy()
+    keep = budget_bytes // 4
+    if a.size <= keep:
+        return a
+    idx = np.sort(np.random.RandomState(seed).choice(a.size, size=keep, replace=False))
+    return np.ascontiguousarray(a.reshape(-1)[idx])
+
+
+def dump_outputs(path, w, images, world, rank):
+    """--dump-outputs: what a caller of the timed step holds after the last timed step, i.e. the images
+    rasterize_core returned and the gradients its backward left in the leaves (vertices; the texture
+    atlas in rgbsd mode, after the ranks' all_reduce with N > 1), as <name>.npy (<name>_rank<r>.npy
+    with N > 1) in float32.  Each output gets a fixed share of the byte budget and is sampled
+    (dump_sample) when it is larger: at the headline size the images are (84 MB against 48 MB)."""
+    os.makedirs(path, exist_ok=True)
+    outs = {"images": images, "grad_vertices": w["proj"].grad,
+            "grad_textures": None if w["tex"] is None else w["tex"].grad}
+    for seed, (name, share) in enumerate(DUMP_SHARES):
+        if outs[name] is None:
+            continue
+        a = dump_sample(outs[name], int(DUMP_BUDGET_BYTES * share) // world, 4000 + seed)
+        np.save(os.path.join(path, name + ("_rank%d" % rank if world > 1 else "") + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.pmc_child:
@@ -488,6 +534,9 @@ def main():
         return count_child(args)
     if args.gpus < 1:
         sys.stderr.write("bench.py: --gpus must be >= 1\n")
+        sys.exit(2)
+    if args.steps < 1 or args.warmup < 0:
+        sys.stderr.write("bench.py: --steps must be >= 1 and --warmup >= 0\n")
         sys.exit(2)
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
@@ -518,7 +567,46 @@ def main():
     ms_per_step = elapsed / args.steps * 1e3
     px = world * args.batch * args.image_size ** 2 * args.steps
     value = px / elapsed / 1e6
+    images = images.detach()  # release the last timed step's autograd graph
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, w, images, world, rank)
 
+    total_bytes = kernel_bytes(w, args)[1]
+    res = {
+        "metric": "rasterize Mpixels/s fwd+bwd, 256² batch=64; % HBM roofline at 1 & 8 GPU",
+        "value": round(value, 3),
+        "unit": "Mpixels/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (ico-sphere, jittered per item, random texture atlas)",
+        "config": {"workload": "ico-sphere L%d (V=%d, F=%d), %d items/GPU, %d^2 output (AA, %d^2 internal), %s"
+                               % (args.level, w["V"], w["F"], args.batch, args.image_size, 2 * args.image_size,
+                                  "rgb+sil+depth" if args.mode == "rgbsd" else "silhouettes"),
+                   "global_batch": world * args.batch, "image_size": args.image_size, "faces": w["F"],
+                   "channels": w["C"], "parallelism": "batch-sharded dp%d" % world},
+        # host time to enqueue the timed steps (Python, autograd, ctypes, launches): below ms_per_step,
+        # the run is GPU-bound
+        "host_ms_per_step": round(host_elapsed / args.steps * 1e3, 4),
+        # the step's compulsory HBM bytes (kernel_bytes) over its time, against the HBM peak
+        "step_roofline_frac": round(total_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+    }
+    if args.full:
+        res.update(full_measurements(args, w, world, rank, dev, images))
+    if rank == 0:
+        print(json.dumps(res), flush=True)
+    if world > 1:
+        torch.distributed.destroy_process_group()
+
+
+def full_measurements(args, w, world, rank, dev, images):
+    """--full: what the bench measures beside the headline figure, after the timed steps (`images`:
+    the last timed step's, detached).  Returns the fields it adds to the result line."""
     # the shared-gradient all_reduce that every timed step above includes, timed on its own (one
     # warm-up was the steps', then the best of 3, max over ranks), like gather_ms below
     allreduce_ms = None
@@ -656,24 +744,6 @@ def main():
     limiter = closest if fracs[closest] >= 0.6 else "latency"
 
     res = {
-        "metric": "rasterize Mpixels/s fwd+bwd, 256² batch=64; % HBM roofline at 1 & 8 GPU",
-        "value": round(value, 3),
-        "unit": "Mpixels/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic (ico-sphere, jittered per item, random texture atlas)",
-        "config": {"workload": "ico-sphere L%d (V=%d, F=%d), %d items/GPU, %d^2 output (AA, %d^2 internal), %s"
-                               % (args.level, w["V"], w["F"], args.batch, args.image_size, 2 * args.image_size,
-                                  "rgb+sil+depth" if args.mode == "rgbsd" else "silhouettes"),
-                   "global_batch": world * args.batch, "image_size": args.image_size, "faces": w["F"],
-                   "channels": w["C"], "parallelism": "batch-sharded dp%d" % world},
-        "host_ms_per_step": round(host_elapsed / args.steps * 1e3, 4),
         "host_ms_per_step_idle_gpu": round(host_idle_ms, 4),
         "host_ms_per_step_autograd_single_thread": round(host_single, 4),
         # achieved / peak / frac are against the HBM roof (the contract's "bound"); the VALU roof beside
@@ -699,7 +769,6 @@ def main():
         "fwd_face_tests_per_px": None if ftr is None else ftr.get("tests_per_px"),
         "fwd_gtests_per_s": None if ftr is None else ftr.get("gtests_per_s"),
         "face_test_rate": ftr,
-        "step_roofline_frac": round(total_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
     }
     if graph_ms is not None:
         # the same step replayed from a captured HIP graph (not the headline value)
@@ -713,10 +782,7 @@ def main():
         res["gather_ms"] = round(gather_ms, 4)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    if world > 1:
-        torch.distributed.destroy_process_group()
+    return res
 
 
 if __name__ == "__main__":

@@ -21,7 +21,13 @@ def golden():
     import numpy as np
 
     def load(name):
-        return dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+        d = dict(np.load(os.path.join(GOLDEN, name + ".npz")))
+        if "grad_up_seed" in d:
+            # the upstream gradient stored as its seed (make_golden.py draws it as N(0,1) in the
+            # images' shape from RandomState(seed)): 1 MB of noise would put the file over 1 MiB
+            seed = int(d.pop("grad_up_seed"))
+            d["grad_up"] = np.random.RandomState(seed).normal(size=d["images"].shape).astype(np.float32)
+        return d
     return load
 
 

@@ -35,11 +35,11 @@ def test_world_size_mismatch_exits_nonzero():
 
 @pytest.mark.gpu
 def test_bench_cli_two_ranks_gloo():
-    """`bench.py --gpus 2 --dist-backend gloo` on the one-GPU box: the script launches its two
+    """`bench.py --gpus 2 --dist-backend gloo --full` on the one-GPU box: the script launches its two
     ranks, each renders its own 64 headline items, and rank 0 prints one line with n_gpus = 2,
-    global_batch = 128 and the all-gather time of the rank images."""
+    global_batch = 128 and (--full) the all-gather time of the rank images."""
     cmd = [sys.executable, "-u", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo",
-           "--steps", "3", "--warmup", "1", "--no-pmc", "--no-cpu-baseline"]
+           "--steps", "3", "--warmup", "1", "--full", "--no-pmc", "--no-cpu-baseline"]
     p = subprocess.run(cmd, env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=110)
     assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
@@ -53,6 +53,62 @@ def test_bench_cli_two_ranks_gloo():
     assert res["allreduce_ms"] is not None and res["allreduce_ms"] > 0
     assert res["allreduce_bytes"] == 3 * 288 * 288 * 4
     assert res["value"] > 0 and res["steps"] == 3
+
+
+def test_dump_sample_is_fixed():
+    """--dump-outputs' sampling: an output within its byte budget is written whole, a larger one as
+    budget / 4 of its flattened elements, the same ones (in index order) for the same shape and seed."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    t = torch.arange(5 * 7 * 11, dtype=torch.float64).reshape(5, 7, 11)
+    whole = bench.dump_sample(t, 4 * t.numel(), 1)
+    assert whole.dtype == np.float32 and whole.shape == (5, 7, 11) and np.array_equal(whole, t.numpy())
+    a, b = bench.dump_sample(t, 400, 1), bench.dump_sample(t + 0, 400, 1)
+    assert a.dtype == np.float32 and a.shape == (100,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a.min() >= 0 and a.max() < t.numel()  # distinct elements, in order
+    assert not np.array_equal(a, bench.dump_sample(t, 400, 2))
+
+
+@pytest.mark.gpu
+def test_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps 2 --warmup 1 --dump-outputs DIR` (8 level-2 items at 64^2):
+    the line carries the headline fields and none of --full's, --steps sets the timed steps, and DIR
+    holds the last step's images and gradients in float32; a second run writes the same images (the
+    face-index map is deterministic; the gradients are f32 atomic sums of at most 64 * 64 pixel terms
+    per element, whose order may differ from run to run: each addition rounds by at most 2^-24 of the
+    running sum, so two runs differ by at most 4096 * 2^-23 = 5e-4 of an element's summed magnitudes
+    in the worst case and by about sqrt(4096) * 2^-24 = 4e-6 typically; bound: 1e-4 of the largest
+    element)."""
+    import numpy as np
+    outs = []
+    for d in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+               "--batch", "8", "--level", "2", "--image-size", "64", "--dump-outputs", str(tmp_path / d)]
+        p = subprocess.run(cmd, env=_env(), cwd=ROOT, capture_output=True, text=True, timeout=110)
+        assert p.returncode == 0, (p.returncode, p.stderr[-2000:])
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        res = json.loads(lines[0])
+        assert res["steps"] == 2 and res["warmup"] == 1 and res["n_gpus"] == 1
+        assert res["unit"] == "Mpixels/s" and res["higher_is_better"] is True and res["dtype"] == "f32"
+        assert res["ms_per_step"] > 0
+        # value and ms_per_step say the same (ms_per_step is rounded to 1e-4 ms, value to 1e-3)
+        assert abs(res["value"] - 8 * 64 * 64 / (res["ms_per_step"] * 1e-3) / 1e6) \
+            <= res["value"] * 1e-4 / res["ms_per_step"] + 2e-3
+        for k in ("kernels_ms", "roofline", "cpu_baseline", "face_test_rate", "host_ms_per_step_idle_gpu"):
+            assert k not in res
+        assert sorted(os.listdir(str(tmp_path / d))) == ["grad_textures.npy", "grad_vertices.npy", "images.npy"]
+        outs.append({n: np.load(str(tmp_path / d / (n + ".npy"))) for n in ("images", "grad_vertices", "grad_textures")})
+    a, b = outs
+    assert a["images"].shape == (8, 5, 64, 64) and a["grad_vertices"].shape == (8, 162, 3)
+    assert a["grad_textures"].ndim == 3 and a["grad_textures"].shape[0] == 3
+    for n in a:
+        assert a[n].dtype == np.float32 and np.isfinite(a[n]).all() and np.abs(a[n]).max() > 0
+    assert np.array_equal(a["images"], b["images"])
+    for n in ("grad_vertices", "grad_textures"):
+        assert np.abs(a[n] - b[n]).max() <= 1e-4 * np.abs(a[n]).max()
 
 
 @pytest.mark.gpu

@@ -11,7 +11,7 @@ for E in ${ENVS:-base}; do
   i=$((i+1))
   EV=""
   if [ "$E" != base ]; then EV=${E//,/ }; fi
-  env $EV timeout -k 10 300 python bench.py --steps ${STEPS:-30} --warmup 3 --no-cpu-baseline --no-pmc > $OUT/bench_${i}_$r.log 2>&1
+  env $EV timeout -k 10 300 python bench.py --steps ${STEPS:-30} --warmup 3 --full --no-cpu-baseline --no-pmc > $OUT/bench_${i}_$r.log 2>&1
   rc=$?; echo "$E rc=$rc: $(python -c "import json,sys; d=json.loads(open('$OUT/bench_${i}_$r.log').read().strip().splitlines()[-1]); print(d['kernels_ms'], d['ms_per_step'])")"
   if [ $rc -ne 0 ]; then exit $rc; fi
 done

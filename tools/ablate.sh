@@ -31,7 +31,7 @@ for V in $VARIANTS; do
   EV=""
   for d in ${V//,/ }; do case $d in @*) EV="$EV ${d#@}";; esac; done
   if [ -z "$NOHEAD" ]; then
-  env $EV NR_LIB_PATH=$OUT/lib/libnr_$i.so timeout -k 10 300 python bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --no-pmc --no-count > $OUT/bench_${i}_$r.log 2>&1
+  env $EV NR_LIB_PATH=$OUT/lib/libnr_$i.so timeout -k 10 300 python bench.py --steps ${STEPS:-10} --warmup 3 --full --no-cpu-baseline --no-pmc --no-count > $OUT/bench_${i}_$r.log 2>&1
   rc=$?; echo "$V rc=$rc: $(python -c "import json,sys; d=json.loads(open('$OUT/bench_${i}_$r.log').read().strip().splitlines()[-1]); print(d['kernels_ms'], d['ms_per_step'])")"
   if [ $rc -ne 0 ]; then exit $rc; fi
   fi

@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 TAG=${1:-pipe}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-PROBE_ARGS="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-pmc" timeout -k 10 600 bash tools/pmc_probe.sh $TAG/h \
+PROBE_ARGS="bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-pmc" timeout -k 10 600 bash tools/pmc_probe.sh $TAG/h \
   "TA_TA_BUSY_sum TA_FLAT_READ_WAVEFRONTS_sum TD_TD_BUSY_sum GRBM_GUI_ACTIVE" \
   "TCP_PENDING_STALL_CYCLES_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCP_TCC_ATOMIC_WITHOUT_RET_REQ_sum" \
   "TCC_HIT_sum TCC_MISS_sum" \

@@ -15,7 +15,7 @@ if [ $rc -ne 0 ]; then exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; tail -1 $OUT/smoke.log
 if [ $rc -ne 0 ]; then exit $rc; fi
-timeout -k 10 400 python bench.py > $OUT/bench.log 2>&1
+timeout -k 10 400 python bench.py --full > $OUT/bench.log 2>&1
 rc=$?; echo "bench rc=$rc"; tail -1 $OUT/bench.log | cut -c1-600
 if [ $rc -ne 0 ]; then exit $rc; fi
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python3 bench.py --no-cpu-baseline --no-pmc --no-count > $OUT/prof.log 2>&1

@@ -9,7 +9,7 @@ i=0
 while read -r PASS; do
   [ -z "$PASS" ] && continue
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $PASS --output-format csv -d $OUT/p$i -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-pmc > $OUT/p$i.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc $PASS --output-format csv -d $OUT/p$i -o run -- python3 bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-pmc > $OUT/p$i.log 2>&1
   rc=$?; echo "pass $i ($PASS) rc=$rc"
   if [ $rc -ge 124 ]; then exit $rc; fi
 done <<'PASSES'

@@ -18,7 +18,7 @@ for PASS in "$@"; do
   ok=1
   for c in $PASS; do grep -qx "$c" $OUT/names.txt || { echo "pass $i: no counter $c"; ok=0; }; done
   [ $ok = 1 ] || continue
-  timeout -k 10 120 rocprofv3 --pmc $PASS --output-format csv -d $OUT/p$i -o run -- python3 ${PROBE_ARGS:-bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-pmc} > $OUT/p$i.log 2>&1
+  timeout -k 10 120 rocprofv3 --pmc $PASS --output-format csv -d $OUT/p$i -o run -- python3 ${PROBE_ARGS:-bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-pmc} > $OUT/p$i.log 2>&1
   rc=$?; echo "pass $i ($PASS) rc=$rc"
   if [ $rc -ne 0 ]; then exit $rc; fi
 done
