@@ -220,9 +220,6 @@ struct BwdPix {
 // HOT: the shared-window flush (BwdArgs.face_hot) compiled in; its instantiations run only when the
 // caller passes face_hot (its per-face id load and address select cost the headline's backward 4 %,
 // 0.194 -> 0.202 ms, when compiled into the plain instantiation, gpurun_out/nh)
-#ifdef NR_ABL_S1LOAD
-__device__ float4* g_abl_prod;  // timing builds only: the per-pixel product planes (zeroed)
-#endif
 template <int FEAT, int NPX, int CC = 0, bool HOT = false>
 __global__ __launch_bounds__(2 * NT / NPX) __attribute__((amdgpu_waves_per_eu((FEAT & 1) ? 3 : (NPX == 1 ? 6 : 4), 8))) void k_raster_bwd(BwdArgs a, Geom g, Shade sh_in) {
     constexpr bool LIT = (FEAT & 1) != 0, BG = (FEAT & 2) != 0, SILO = (FEAT & 4) != 0;
@@ -337,11 +334,7 @@ __global__ __launch_bounds__(2 * NT / NPX) __attribute__((amdgpu_waves_per_eu((F
         }
     };
     NR_TSTAMP(0);
-#ifndef NR_ABL_NOSTENCIL
     halo_prefetch();  // in flight during step 1
-#else
-    (void)halo_prefetch;
-#endif
 
     // ---- 1. image + upstream gradient (LDS), and the stencil-independent gradient terms ---------
     BwdPix P[NPX];
@@ -402,45 +395,6 @@ __global__ __launch_bounds__(2 * NT / NPX) __attribute__((amdgpu_waves_per_eu((F
             I2[k][0] = 1.f;
             continue;
         }
-#if defined(NR_ABL_S1ZERO) || defined(NR_ABL_S1LOAD)
-        // timing builds only (the bound of a backward that reads its per-pixel products instead of
-        // recomputing them; values are placeholders, not gradients): S1ZERO recomputes nothing, S1LOAD
-        // loads 48 B per foreground pixel from a lane-ordered buffer (3 coalesced float4 planes)
-        {
-            float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f), v1 = v0, v2 = v0;
-#ifdef NR_ABL_S1LOAD
-            const size_t np = (size_t)gridDim.x * gridDim.y * blockDim.x * NPX;
-            const size_t pi = (((size_t)blockIdx.y * gridDim.x + blockIdx.x) * blockDim.x + t) * NPX + k;
-            v0 = g_abl_prod[pi];
-            v1 = g_abl_prod[np + pi];
-            v2 = g_abl_prod[2 * np + pi];
-#endif
-            const float fh = (float)(q.fi & 255) * (1.f / 255.f);
-            q.w[0] = 0.3f + v0.x;
-            q.w[1] = 0.3f + v0.y;
-            q.w[2] = 0.4f + v0.z;
-            I2[k][0] = fh + v0.w;
-            I2[k][1] = 1.f - fh + v1.x;
-            I2[k][2] = 0.5f * fh + v1.y;
-            I2[k][3] = 1.f;
-            I2[k][4] = 2.f + fh + v1.z;
-            q.ay = 0.5f + v1.w;
-            q.by = 0.5f + v2.x;
-            q.ax = 0.25f + v2.y;
-            q.bx = 0.75f + v2.z;
-            q.grgb[0] = G[0];
-            q.grgb[1] = G[1];
-            q.grgb[2] = G[2];
-#pragma unroll
-            for (int j = 0; j < 3; j++) q.gz[j] = G[MAXC - 1] * 0.01f * q.w[j] + v2.w;
-            if (want_tex) {
-                q.wx = (q.fi % 72) * 4;
-                q.wy = (q.fi / 72) * 4;
-                q.pos = 5;
-            }
-            continue;
-        }
-#endif
         Face f = load_face_rec(frb + q.fi * FACE_REC);
         // the texture record with the face record: one round trip for both (unconditional, so that
         // no branch join needs its value: without rgb it reads the face record's first 32 bytes)
@@ -571,7 +525,6 @@ __global__ __launch_bounds__(2 * NT / NPX) __attribute__((amdgpu_waves_per_eu((F
         I2[k][3] = Sl ? 1.f : dep;
         I2[k][4] = dep;
     }
-#ifndef NR_ABL_NOSTENCIL  // timing builds only: no LDS staging, halo or pair terms (placeholder stencil)
 #pragma unroll
     for (int k = 0; k < NPX; k++) store_ig((ly0 + 4 * k + 1) * HW_ + (lx + 1), I2[k], G2[k]);
     // halo ring: image and upstream gradient only
@@ -662,10 +615,6 @@ __global__ __launch_bounds__(2 * NT / NPX) __attribute__((amdgpu_waves_per_eu((F
         }
     }
     __syncthreads();
-#else
-    float gF[NPX][9];
-    (void)h_live;
-#endif
 #pragma unroll
     for (int k = 0; k < NPX; k++) {
         BwdPix& q = P[k];
@@ -673,13 +622,9 @@ __global__ __launch_bounds__(2 * NT / NPX) __attribute__((amdgpu_waves_per_eu((F
         for (int j = 0; j < 9; j++) gF[k][j] = 0.f;
         if (q.fi < 0) continue;
         const int py = ty0 + ly0 + 4 * k;
-#ifndef NR_ABL_NOSTENCIL
         const int li = (ly0 + 4 * k + 1) * HW_ + (lx + 1);
         const float gx = stencil_pair(a, own_px[k], s_px[li - 1], px, S);
         const float gy = stencil_pair(a, own_py[k], s_py[li - HW_], py, S);
-#else
-        const float gx = (I2[k][0] - I2[k][1]) * G2[k][0] * 7.f, gy = (I2[k][2] - I2[k][MAXC - 1]) * G2[k][1] * 5.f;
-#endif
         if (wlate && (gx != 0.f || gy != 0.f)) {
             // silhouettes only: the stencil is zero away from silhouette edges, so only these pixels
             // fetch their face and weights (the same computation as in step 1)
@@ -809,11 +754,7 @@ __global__ __launch_bounds__(2 * NT / NPX) __attribute__((amdgpu_waves_per_eu((F
                 if (LIT) an += on ? rw * rn : 0.f;  // corner-normal gradient tt = 3 corner + axis
             };
             // one loop over both pixel rows (2- and 4-member steps measured slower)
-#ifndef NR_ABL_NOGATHER  // timing builds only: no member loop
             for (; mine; mine &= mine - 1) member(rbase + __builtin_ctz(mine) * REC, true);
-#else
-            (void)rbase;
-#endif
         }
         // reduce-scatter over the 4 member chunks (lanes t, t+16, t+32, t+48) with the gfx950 lane
         // swaps (VALU, no LDS round trip): lane (t, c) ends with the chunk total of value c
@@ -841,15 +782,7 @@ __global__ __launch_bounds__(2 * NT / NPX) __attribute__((amdgpu_waves_per_eu((F
                 hpos[2 * phid] = pwx;
                 hpos[2 * phid + 1] = pwy;
             }
-#ifdef NR_ABL_NOATOM  // timing builds only: no flush atomics
-            if ((tex_lane || face_lane) && fv == 12345.f) unsafeAtomicAdd(dst, fv);
-#elif defined(NR_ABL_NOTEXFLUSH)  // timing builds only: no texture-window flush atomics
-            if (((tex_lane && fv == 12345.f) || face_lane) && fv != 0.f) unsafeAtomicAdd(dst, fv);
-#elif defined(NR_ABL_NOGFFLUSH)  // timing builds only: no face-gradient flush atomics
-            if ((tex_lane || (face_lane && fv == 12345.f)) && fv != 0.f) unsafeAtomicAdd(dst, fv);
-#else
             if ((tex_lane || face_lane) && fv != 0.f) unsafeAtomicAdd(dst, fv);
-#endif
             if (win) {
                 pend = sw ? v : pend + v;
                 pwx = wx;
@@ -909,11 +842,7 @@ __global__ __launch_bounds__(2 * NT / NPX) __attribute__((amdgpu_waves_per_eu((F
             const float v = gsel * wsel;
             // the texel index as sample_texture clamps it (a clamped corner has weight 0)
             const int idx = min(max(direct_base(__float_as_int(rb.w)) + col + row * sh.tv.W, 0), HW - 1);
-#ifdef NR_ABL_NODIRECT  // timing builds only: no direct-sample atomics
-            if (slot >= 0 && ch < 3 && v == 12345.f) unsafeAtomicAdd(gtb + idx * 4 + ch, v);
-#else
             if (slot >= 0 && ch < 3 && v != 0.f) unsafeAtomicAdd(gtb + idx * 4 + ch, v);
-#endif
         }
     }
     NR_TSTAMP(6);
@@ -967,20 +896,6 @@ void launch_bwd_v(dim3 grid, hipStream_t st, const BwdArgs& ba, const Geom& g, c
 // passes face_hot for no other (nr_rasterize_backward)
 template <int FEAT>
 void launch_bwd(dim3 grid, hipStream_t st, const BwdArgs& ba, const Geom& g, const Shade& sh) {
-#ifdef NR_ABL_S1LOAD
-    {  // timing builds only: a zeroed buffer of 3 float4 planes, one entry per (thread, pixel) of the grid
-        static float4* buf = nullptr;
-        static size_t have = 0;
-        const size_t need = (size_t)grid.x * grid.y * NT * 2 * 3 * sizeof(float4);
-        if (need > have) {
-            if (buf) (void)hipFree(buf);
-            if (hipMalloc(&buf, need) != hipSuccess || hipMemset(buf, 0, need) != hipSuccess ||
-                hipMemcpyToSymbol(HIP_SYMBOL(g_abl_prod), &buf, sizeof(buf)) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
-                abort();
-            have = need;
-        }
-    }
-#endif
     if constexpr (FEAT == 0) {
         if (ba.face_hot) {
             launch_bwd_v<FEAT, true>(grid, st, ba, g, sh);

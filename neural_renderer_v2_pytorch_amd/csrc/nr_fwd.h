@@ -76,13 +76,9 @@ __global__ __launch_bounds__(256) void k_face_setup(const float* __restrict__ ve
                 float4* rec = reinterpret_cast<float4*>(s_frec + t * FACE_REC);
                 rec[0] = make_float4(c[0], c[1], c[2], c[3]);
                 rec[1] = make_float4(c[4], c[5], c[6], c[7]);
-#ifdef NR_REC48
-                rec[2] = make_float4(c[8], __int_as_float(flags), 0.f, 0.f);
-#else
                 rec[2] = make_float4(c[8], face_rcp(c[2]), face_rcp(c[5]), face_rcp(c[8]));
                 rec[3] = make_float4(face_rcp(c[2] + 1e-10f), face_rcp(c[5] + 1e-10f), face_rcp(c[8] + 1e-10f),
                                      __int_as_float(flags));
-#endif
                 if (fnorm) {
                     // face normal cross(v1 - v0, v2 - v1) (rasterize.py:166-170; torch.cross component order)
                     const float a0 = c[3] - c[0], a1 = c[4] - c[1], a2 = c[5] - c[2];
@@ -515,9 +511,7 @@ __device__ __forceinline__ void face_commit(const float4* s_face, int slot, floa
 }
 
 constexpr int ZCULL_MIN = 512;  // candidates of a bin (first bin-mask round)
-#ifndef NR_ZREFRESH
-#define NR_ZREFRESH 255
-#endif
+constexpr int ZREFRESH = 255;   // (mask) the ZCULL bound is refreshed at most every ZREFRESH + 1 faces
 // one wave's walk of the n staged faces over its 8x8 block u of the bin (pixel (xp, yp) per lane): the
 // ballot takes the staged faces whose block mask (face_block_mask: bbox, and with CULL the edge cull)
 // has bit u, then the per-face test runs in ascending order
@@ -525,15 +519,15 @@ constexpr int ZCULL_MIN = 512;  // candidates of a bin (first bin-mask round)
 // diagnostic build: face tests, faces walked, commit batches, walks (nr_count_read)
 __device__ unsigned long long g_fwd_count[4];
 #endif
-template <int FST, bool SLOT, bool ZCULL = false, typename MT = uint16_t, bool Q16 = false>
-__device__ __forceinline__ void walk_block(const float4* __restrict__ s_face, const MT* __restrict__ s_bm, int u,
+template <int FST, bool SLOT, bool ZCULL = false>
+__device__ __forceinline__ void walk_block(const float4* __restrict__ s_face, const uint16_t* __restrict__ s_bm, int u,
                                            int n, int lane, float xp, float yp, float near, float far, float delta,
                                            float& depth_min, int& best) {
     int pend = -1;               // staging slot of my pixel's pending face
     unsigned long long occ = 0;  // the wave's pixels with a pending face
     // (ZCULL: the deep variant's bins of >= ZCULL_MIN candidates) a face whose nearest corner lies
     // behind every pixel's current depth (the wave's maximum, refreshed when a commit has changed a
-    // depth since, at most every NR_ZREFRESH + 1 faces) fails the pass test's depth reject at each of
+    // depth since, at most every ZREFRESH + 1 faces) fails the pass test's depth reject at each of
     // them (depth_min only decreases; NaN bounds are kept): it is dropped in the ballot, with 63
     // others, instead of walked alone.  Car forward 0.625 -> 0.601 ms; the 50k torus (deep bins of low
     // depth complexity) 0.118 -> 0.120 ms; on every bin of the headline and the torus the gate-free
@@ -544,7 +538,7 @@ __device__ __forceinline__ void walk_block(const float4* __restrict__ s_face, co
     unsigned long long cnt_walked = 0, cnt_commits = 0;
 #endif
     for (int c0 = 0; c0 < n; c0 += 64) {
-        if (ZCULL && dirty && (c0 & NR_ZREFRESH) == 0) {
+        if (ZCULL && dirty && (c0 & ZREFRESH) == 0) {
             zmax = wave_max(depth_min);
             dirty = false;
         }
@@ -569,10 +563,8 @@ __device__ __forceinline__ void walk_block(const float4* __restrict__ s_face, co
             // each comparison straight to a lane mask (v_cmp into an SGPR pair; the masks combine on the
             // scalar unit): a ballot of the combined boolean costs a v_cndmask + v_cmp per face to
             // rebuild the mask.  !(a < b) is "a >= b or unordered" (UGE), !(a > b) is ULE.
-            // (Q16: a 4x4 quarter, lanes 0-15 only)
             const unsigned long long pre = lane_mask_uge(depth_min, q1.x) & lane_mask_uge(xp, q0.x) &
-                                           lane_mask_ule(xp, q0.y) & lane_mask_uge(yp, q0.z) & lane_mask_ule(yp, q0.w) &
-                                           (Q16 ? 0xffffull : ~0ull);
+                                           lane_mask_ule(xp, q0.y) & lane_mask_uge(yp, q0.z) & lane_mask_ule(yp, q0.w);
             unsigned long long cov = 0;
             if (pre) {
                 // .cu:107-116: c1 = (yp - y0) A - B (xp - x0), c3 = (yp - y2) E - F (xp - x2),
@@ -602,7 +594,7 @@ __device__ __forceinline__ void walk_block(const float4* __restrict__ s_face, co
 #ifdef NR_COUNT_TESTS
     if (occ) cnt_commits++;
     if (lane == 0) {
-        atomicAdd(&g_fwd_count[0], cnt_walked * (Q16 ? 16ull : 64ull));
+        atomicAdd(&g_fwd_count[0], cnt_walked * 64ull);
         atomicAdd(&g_fwd_count[1], cnt_walked);
         atomicAdd(&g_fwd_count[2], cnt_commits);
         atomicAdd(&g_fwd_count[3], 1ull);
@@ -635,7 +627,7 @@ __device__ __forceinline__ void walk_quarter4(const float4* __restrict__ s_face,
     unsigned long long cnt_walked = 0, cnt_commits = 0;
 #endif
     for (int c0 = 0; c0 < n; c0 += 64) {
-        if (dirty && (c0 & NR_ZREFRESH) == 0) {  // (as walk_block's ZCULL)
+        if (dirty && (c0 & ZREFRESH) == 0) {  // (as walk_block's ZCULL)
             zmax = wave_max(depth_min);
             dirty = false;
         }
@@ -1117,19 +1109,10 @@ __global__ __launch_bounds__(NTF) __attribute__((amdgpu_waves_per_eu(FWD_WPE, 8)
                         const int px = (q & 7) * 4 + (lane & 3), py = (q >> 3) * 4 + ((lane >> 2) & 3);
                         const bool on = lane < 16;
                         const int pix = py * COARSE + px;
-#ifndef NR_NO_W4
                         float dm = s_dm[pix];  // (lanes 16-63: copies of lanes 0-15, walk_quarter4)
-#else
-                        float dm = on ? s_dm[pix] : -INFINITY;  // lanes 16-63: no pixel (and no share of the wave's depth maximum)
-#endif
                         int best = on ? s_best[pix] : -1;
                         const float xq = pix_center_div(bx0 + px, S), yq = pix_center_div(by0 + py, S);
-#ifndef NR_NO_W4
                         walk_quarter4<FCAP>(s_face, s_q, q, n, lane, xq, yq, near, far, delta, dm, best);
-#else
-                        walk_block<FCAP, false, true, uint64_t, true>(s_face, s_q, q, n, lane, xq, yq, near, far, delta,
-                                                                      dm, best);
-#endif
                         if (on) {
                             s_dm[pix] = dm;
                             s_best[pix] = best;

@@ -64,11 +64,6 @@ __global__ void k_selftest_div(const float* __restrict__ a, const float* __restr
     qi[i] = x / y;
 }
 
-#ifdef NR_ABL_EXTRAK
-// (timing builds) an empty dispatch: its cost in the step is one launch and drain
-__global__ void k_abl_empty(int) {}
-#endif
-
 // ==================================================================================================
 extern "C" {
 
@@ -94,10 +89,13 @@ size_t nr_workspace_bytes(int batch_size, int num_faces, int image_size) {
 // A side stream per (host thread, device) for the split forward, with its fork / join events; created
 // on first use outside a stream capture (null: no split for this call).  The thread's table releases
 // them when the thread ends (a worker pool's recycled threads do not accumulate streams).  No
-// synchronisation there: hipStreamDestroy of a stream with queued work returns at once and releases it
-// when the work is done, and a synchronising call from an exiting thread would invalidate another
-// thread's graph capture in global capture mode; the destroys themselves run in this thread's relaxed
-// capture mode for the same reason.  Errors are ignored (at process exit the runtime may be gone).
+// synchronisation there: a synchronising call from an exiting thread would invalidate another thread's
+// graph capture in global capture mode, so the code relies on hipStreamDestroy of a stream that may
+// still have queued work neither waiting for that work nor dropping it.  HIP's documentation leaves
+// that open (CUDA's promises it for cudaStreamDestroy): an assumption about the runtime, not a
+// guarantee, and one no test exercises (the exiting-thread test's workers synchronise before they
+// end).  The destroys themselves run in this thread's relaxed capture mode for the same reason.
+// Errors are ignored (at process exit the runtime may be gone).
 struct SideStream {
     hipStream_t s = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;
@@ -119,14 +117,8 @@ struct SideStreamTable {
         if (exch) (void)hipThreadExchangeStreamCaptureMode(&mode);
     }
 };
-#ifndef NR_SPLIT_BUCKET
-#define NR_SPLIT_BUCKET 10
-#endif
-constexpr int SPLIT_BUCKET = NR_SPLIT_BUCKET;  // deep bins: >= 512 candidates
-#ifndef NR_QS_CAP
-#define NR_QS_CAP 16
-#endif
-constexpr int QS_CAP = NR_QS_CAP;  // deep bins per list walked by quadrant blocks (a forward that does not split)
+constexpr int SPLIT_BUCKET = 10;  // deep bins: >= 512 candidates
+constexpr int QS_CAP = 16;        // deep bins per list walked by quadrant blocks (a forward that does not split)
 SideStream* side_stream(hipStream_t st) {
     static thread_local SideStreamTable table;
     SideStream* tab = table.tab;
@@ -164,6 +156,38 @@ static int deep_slots_per_xcd() {
         __atomic_store_n(&cached[dev], 2 * max(cus / 8, 1), __ATOMIC_RELAXED);
     }
     return __atomic_load_n(&cached[dev], __ATOMIC_RELAXED);
+}
+
+// One k_raster_fwd launch: its instantiation (k_raster_fwd's template parameters, nr_fwd.h) and the part
+// of a deep-first list it walks (ordered_bin: 0 every bin, 1 a split's deep prefix, 2 a split's rest,
+// 3 every bin plus the quadrant blocks of the deepest)
+struct FwdVariant {
+    int ntf;     // NTF: block threads, 256 or 1024
+    bool shade;  // SHADE: k_shade's work fused in
+    int cc;      // CC: compile-time channels, MAXC or 4 (256 threads with SHADE only; 0: at run time)
+    bool dq;     // DQ: the dealt-quarter walk (1024 threads only)
+    int part;
+};
+// The forward's kernels by run-time choice: the setup with or without the gather from vertices, the
+// eight k_raster_fwd instantiations the library holds, and the separate shading launch's by its lights
+// (1) / backgrounds (2) feature mask.  (The compiler lays the instantiations out in the code object in
+// the order these functions first name them.)
+using SetupFn = decltype(&k_face_setup<true>);
+static SetupFn setup_kernel(bool gather) { return gather ? k_face_setup<true> : k_face_setup<false>; }
+using RasterFwdFn = decltype(&k_raster_fwd<1024, true>);
+static RasterFwdFn raster_fwd_kernel(const FwdVariant& v) {
+    if (v.shade && v.ntf == 1024 && !v.dq) return k_raster_fwd<1024, true>;
+    if (v.shade && v.ntf == 256 && v.cc == MAXC) return k_raster_fwd<256, true, MAXC>;
+    if (v.shade && v.ntf == 256) return v.cc == 4 ? k_raster_fwd<256, true, 4> : k_raster_fwd<256, true>;
+    if (v.shade) return k_raster_fwd<1024, true, 0, true>;
+    if (v.ntf == 256) return k_raster_fwd<256, false>;
+    return v.dq ? k_raster_fwd<1024, false, 0, true> : k_raster_fwd<1024, false>;
+}
+using ShadeFn = decltype(&k_shade_px<0>);
+static ShadeFn shade_kernel(bool per_pixel, int feat) {
+    static const ShadeFn px[4] = {k_shade_px<0>, k_shade_px<1>, k_shade_px<2>, k_shade_px<3>};
+    static const ShadeFn quad[4] = {k_shade<0>, k_shade<1>, k_shade<2>, k_shade<3>};
+    return (per_pixel ? px : quad)[feat];
 }
 
 static int run_face_index(const float* vertices, const int32_t* faces_idx, float* face_records, int32_t* fim,
@@ -215,11 +239,7 @@ static int run_face_index(const float* vertices, const int32_t* faces_idx, float
     // wrote every piece)
     const int Bcap = B % 8 == 0 ? max(8, (B / 4 + 7) / 8 * 8) : 0;
     const bool want_split = ordered && fuse && B % 8 == 0 && Bcap <= B;
-#ifndef NR_NO_SPARSE_GROUPS
     const bool sg = ordered && !want_split && setup_groups(g) <= 1024;
-#else
-    const bool sg = false;
-#endif
     if (F > 0) {
         dim3 grid((F + SETUP_FACES - 1) / SETUP_FACES, B);
         const bool rgb = ra && (ra->draw_flags & NR_DRAW_RGB);
@@ -227,17 +247,13 @@ static int run_face_index(const float* vertices, const int32_t* faces_idx, float
         ProfScope _p(P_SETUP, st, true);
         const bool lit = rgb && ra->num_lights > 0;
         const size_t lds = (size_t)setup_lds_words(g.nbins) * 4;
-        if (vertices)
-            nr_launch(k_face_setup<true>, grid, dim3(256), lds, st, vertices, faces_idx, face_records, V, F, S,
-                               draw_backside, bbox, mask, g.nbx, g.nbins, g.nwords,
-                               rgb ? ra->vertices_textures : nullptr, rgb ? ra->vt_batch_stride : 0,
-                               rgb ? ra->num_vertices_textures : 0, rgb ? ra->faces_textures : nullptr,
-                               rgb ? ra->face_uv : nullptr, uv_items, lit ? ra->face_normals : nullptr, pk, zf,
-                               ordered ? bin_part : nullptr, B % 8 == 0, sg ? 1 : 0);
-        else
-            nr_launch(k_face_setup<false>, grid, dim3(256), lds, st, nullptr, nullptr, face_records, V, F, S,
-                               draw_backside, bbox, mask, g.nbx, g.nbins, g.nwords, nullptr, 0, 0, nullptr, nullptr, 0,
-                               nullptr, pk, zf, ordered ? bin_part : nullptr, B % 8 == 0, sg ? 1 : 0);
+        // gathering from vertices, or (no vertices, hence no ra: every texture argument is null) the caller's faces
+        nr_launch(setup_kernel(vertices != nullptr), grid, dim3(256), lds, st, vertices, faces_idx,
+                  face_records, V, F, S, draw_backside, bbox, mask, g.nbx, g.nbins, g.nwords,
+                  rgb ? ra->vertices_textures : nullptr, rgb ? ra->vt_batch_stride : 0,
+                  rgb ? ra->num_vertices_textures : 0, rgb ? ra->faces_textures : nullptr,
+                  rgb ? ra->face_uv : nullptr, uv_items, lit ? ra->face_normals : nullptr, pk, zf,
+                  ordered ? bin_part : nullptr, B % 8 == 0, sg ? 1 : 0);
         int e = check_launch("k_face_setup");
         if (e) return e;
         if (lit && V > 0) {
@@ -253,11 +269,7 @@ static int run_face_index(const float* vertices, const int32_t* faces_idx, float
     // 1024-thread variant on the caller's stream, the rest in the 256-thread variant on a side stream at
     // the same time: a shallow bin's 16 waves in the 1024-thread variant mostly wait for their block's
     // slowest wave, where the 256-thread variant deals its 16 8x8 blocks to 4 waves
-    int* split_cnt = (int*)((char*)bin_order + align_up((size_t)B * g.nbins * 4));
-    SideStream* side = nullptr;
-#ifndef NR_NO_SPLIT
-    if (want_split) side = side_stream(st);
-#endif
+    SideStream* side = want_split ? side_stream(st) : nullptr;
     // the deep launch takes at most 7/8 of one XCD's slots for 1024-thread blocks per list (two per CU,
     // by their waves and LDS), so every deep bin is dispatched at once: a deep block waiting for a slot
     // starves behind the rest launch's 256-thread blocks, which take every CU space that frees up (at
@@ -271,16 +283,13 @@ static int run_face_index(const float* vertices, const int32_t* faces_idx, float
     // >= 512 candidates (up to QS_CAP of them) are walked by four blocks each, one per 16x16 quadrant
     // (ordered_bin part 3), so the deepest bins, which set the span while most of the chip idles, spread
     // over four CUs
-#ifndef NR_NO_QS
     const bool qs = ordered && !side;
-#else
-    const bool qs = false;
-#endif
     const int lists = B % 8 == 0 ? 8 : 1;
-    const unsigned qs_grid = (unsigned)((long long)g.nbins * B + (qs ? 3 * QS_CAP * lists : 0));
+    // each list's count of deep bins (k_bin_order): a deep-first forward either splits or walks quadrants
+    int* split_cnt = ordered ? (int*)((char*)bin_order + align_up((size_t)B * g.nbins * 4)) : nullptr;
     if (ordered) {
         nr_launch(k_bin_order, dim3(lists), dim3(1024), 0, st, bin_part, setup_groups(g), bin_order, B,
-                           g.nbins, (side || qs) ? split_cnt : nullptr, SPLIT_BUCKET, side ? deep_cap : QS_CAP);
+                           g.nbins, split_cnt, SPLIT_BUCKET, side ? deep_cap : QS_CAP);
         const int e = check_launch("k_bin_order");
         if (e) return e;
     }
@@ -290,91 +299,63 @@ static int run_face_index(const float* vertices, const int32_t* faces_idx, float
     // empty bins leave their -1 face ids unwritten (NrRasterArgs.face_index_sparse): with the fused
     // shading nothing else in this launch reads them, and the backward skips those tiles by the flags
     const int sparse = (ra && ra->face_index_sparse && fuse && binfg) ? 1 : 0;
+    // The launches' variants, decided once; nr_last_launch reports the caller's-stream launch from the
+    // same values.
+    //   fwd:  on the caller's stream: the whole forward, or a split's deep prefix (part 1) in the plain
+    //         1024-thread kernel (the dealt-quarter variant with its four-faces-per-step walk there
+    //         instead: car forward 0.427 -> 0.434 ms, same-box A/B, run record w4b: the deep launch
+    //         takes more of the rest's wave slots).  A deep-first forward that does not split (qs) runs
+    //         the dealt-quarter kernel with the quadrant blocks (part 3).
+    //   rest: a split's other bins (part 2) on the side stream, 256 threads.
+    // cc256: the 256-thread fused kernel's compile-time channels: rgb + sil + depth, or rgba (the car)
+    const int cc256 = sh.C == MAXC ? MAXC : (sh.draw == static_draw(4) ? 4 : 0);
+    const FwdVariant fwd{ntf, fuse, fuse && ntf == 256 ? cc256 : 0, qs, side ? 1 : (qs ? 3 : 0)};
+    const FwdVariant rest{256, true, cc256, false, 2};
+    const dim3 bins(g.nbins, B);
+    // (split: a grid of exactly the cap's blocks: every block past a list's deep prefix exits at once, but
+    // each still needs a 1024-thread slot to be dispatched in; quadrants: 3 more blocks per deep bin)
+    const dim3 fwd_grid = side ? dim3(8 * deep_cap)
+                          : qs ? dim3((unsigned)((long long)g.nbins * B + 3 * QS_CAP * lists)) : bins;
+    const int rs = vertices ? FACE_REC : 9;
+    const auto launch = [&](const FwdVariant& v, dim3 grid, hipStream_t s) {
+        nr_launch(raster_fwd_kernel(v), grid, dim3(v.ntf), 0, s, face_records, rs, bbox, mask, F, g, near, far, delta,
+                  fim, sh, v.shade ? images : nullptr, v.shade ? ra->halo : nullptr, binfg, order, sparse, split_cnt,
+                  v.part, sg ? bin_part : nullptr);
+        return check_launch("k_raster_fwd");
+    };
+    g_last_fwd.store(LaunchRec{fwd.ntf, (fwd.shade ? NR_LAUNCH_FUSED_SHADE : 0) | (fwd.cc ? NR_LAUNCH_STATIC_CHANNELS : 0) |
+                                            (order ? NR_LAUNCH_DEEP_FIRST : 0) | (side ? NR_LAUNCH_SPLIT : 0) |
+                                            (fwd.dq ? NR_LAUNCH_DEALT_QUARTERS : 0) |
+                                            (fwd.part == 3 ? NR_LAUNCH_QUADRANTS : 0)});
+    int e;
     {
         ProfScope _p(P_RASTER, st, side == nullptr);
-        const int rs = vertices ? FACE_REC : 9;
-        g_last_fwd.store(LaunchRec{ntf, (fuse ? NR_LAUNCH_FUSED_SHADE : 0) |
-                                        (fuse && ntf == 256 && (sh.C == MAXC || sh.draw == static_draw(4)) ? NR_LAUNCH_STATIC_CHANNELS : 0) |
-                                        (ordered ? NR_LAUNCH_DEEP_FIRST : 0) | (side ? NR_LAUNCH_SPLIT : 0) |
-                                        (ordered && !side && ntf == 1024 ? NR_LAUNCH_DEALT_QUARTERS : 0) |
-                                        (qs ? NR_LAUNCH_QUADRANTS : 0)});
         if (side) {
             // fork: the side stream waits for the setup and the order; join: the caller's stream waits
             // for the side stream's launch
             if (hipEventRecord(side->fork, st) != hipSuccess || hipStreamWaitEvent(side->s, side->fork, 0) != hipSuccess)
                 return check_launch("hipEventRecord");
-            // (a grid of exactly the cap's blocks: every block past a list's deep prefix exits at once, but
-            // each still needs a 1024-thread slot to be dispatched in)
-            // (the dealt-quarter variant with its four-faces-per-step walk here instead: car forward 0.427 ->
-            // 0.434 ms, same-box A/B, gpurun_out/w4b: the deep launch takes more of the rest's wave slots)
-            nr_launch((k_raster_fwd<1024, true>), dim3(8 * deep_cap), dim3(1024), 0, st, face_records, rs, bbox,
-                               mask, F, g, near, far, delta, fim, sh, images, ra->halo, binfg, order, sparse, split_cnt, 1, nullptr);
-            int e = check_launch("k_raster_fwd");
+            e = launch(fwd, fwd_grid, st);
             if (e) return e;
-            if (sh.C == MAXC)
-                nr_launch((k_raster_fwd<256, true, MAXC>), dim3(g.nbins, B), dim3(256), 0, side->s, face_records, rs,
-                                   bbox, mask, F, g, near, far, delta, fim, sh, images, ra->halo, binfg, order, sparse,
-                                   split_cnt, 2, nullptr);
-            else if (sh.draw == static_draw(4))  // rgba (the car): compile-time channels
-                nr_launch((k_raster_fwd<256, true, 4>), dim3(g.nbins, B), dim3(256), 0, side->s, face_records, rs,
-                                   bbox, mask, F, g, near, far, delta, fim, sh, images, ra->halo, binfg, order, sparse,
-                                   split_cnt, 2, nullptr);
-            else
-                nr_launch((k_raster_fwd<256, true>), dim3(g.nbins, B), dim3(256), 0, side->s, face_records, rs, bbox,
-                                   mask, F, g, near, far, delta, fim, sh, images, ra->halo, binfg, order, sparse, split_cnt, 2, nullptr);
-            e = check_launch("k_raster_fwd");
+            e = launch(rest, bins, side->s);
             if (e) return e;
             if (hipEventRecord(side->join, side->s) != hipSuccess || hipStreamWaitEvent(st, side->join, 0) != hipSuccess)
                 return check_launch("hipEventRecord");
-        } else if (fuse && ntf == 1024 && ordered)  // deep bins, not split (e.g. one item): dealt quarters
-            nr_launch((k_raster_fwd<1024, true, 0, true>), dim3(qs_grid),
-                      dim3(1024), 0, st, face_records, rs, bbox, mask, F, g, near, far, delta, fim, sh, images, ra->halo,
-                      binfg, order, sparse, split_cnt, qs ? 3 : 0, sg ? bin_part : nullptr);
-        else if (fuse && ntf == 1024)
-            nr_launch((k_raster_fwd<1024, true>), dim3(g.nbins, B), dim3(1024), 0, st, face_records, rs, bbox,
-                               mask, F, g, near, far, delta, fim, sh, images, ra->halo, binfg, order, sparse, nullptr, 0, nullptr);
-        else if (fuse && sh.C == MAXC)  // rgb + sil + depth: compile-time channels
-            nr_launch((k_raster_fwd<256, true, MAXC>), dim3(g.nbins, B), dim3(256), 0, st, face_records, rs, bbox,
-                               mask, F, g, near, far, delta, fim, sh, images, ra->halo, binfg, order, sparse, nullptr, 0, nullptr);
-        else if (fuse && sh.draw == static_draw(4))  // rgba: compile-time channels
-            nr_launch((k_raster_fwd<256, true, 4>), dim3(g.nbins, B), dim3(256), 0, st, face_records, rs, bbox,
-                               mask, F, g, near, far, delta, fim, sh, images, ra->halo, binfg, order, sparse, nullptr, 0, nullptr);
-        else if (fuse)
-            nr_launch((k_raster_fwd<256, true>), dim3(g.nbins, B), dim3(256), 0, st, face_records, rs, bbox, mask,
-                               F, g, near, far, delta, fim, sh, images, ra->halo, binfg, order, sparse, nullptr, 0, nullptr);
-        else if (ntf == 256)
-            nr_launch((k_raster_fwd<256, false>), dim3(g.nbins, B), dim3(256), 0, st, face_records, rs, bbox, mask,
-                               F, g, near, far, delta, fim, sh, nullptr, nullptr, binfg, order, 0, nullptr, 0, nullptr);
-        else if (ordered)
-            nr_launch((k_raster_fwd<1024, false, 0, true>), dim3(qs_grid),
-                      dim3(1024), 0, st, face_records, rs, bbox, mask, F, g, near, far, delta, fim, sh, nullptr, nullptr,
-                      binfg, order, 0, split_cnt, qs ? 3 : 0, sg ? bin_part : nullptr);
-        else
-            nr_launch((k_raster_fwd<1024, false>), dim3(g.nbins, B), dim3(1024), 0, st, face_records, rs, bbox,
-                               mask, F, g, near, far, delta, fim, sh, nullptr, nullptr, binfg, order, 0, nullptr, 0, nullptr);
+        } else {
+            e = launch(fwd, fwd_grid, st);
+        }
     }
-    int e = check_launch("k_raster_fwd");
     if (e || !ra || fuse) return e;
+    // the separate shading launch: for a small grid k_shade_px, whose anti-aliased blocks cover 64
+    // output pixels instead of 256
     const int s = ra->anti_aliasing ? S / 2 : S;
+    const bool small = ((long long)s * s + 255) / 256 * B < 4096;
+    const int per_block = small && ra->anti_aliasing ? 64 : 256;
     {
         ProfScope _p(P_SHADE, st, true);
-        if (((long long)s * s + 255) / 256 * B < 4096) {
-            const dim3 grid((unsigned)(((long long)s * s + (ra->anti_aliasing ? 63 : 255)) / (ra->anti_aliasing ? 64 : 256)), B);
-            switch ((sh.nl ? 1 : 0) | (sh.bg ? 2 : 0)) {
-                case 0: nr_launch(k_shade_px<0>, grid, dim3(256), 0, st, face_records, fim, F, S, sh, ra->anti_aliasing, images, ra->halo); break;
-                case 1: nr_launch(k_shade_px<1>, grid, dim3(256), 0, st, face_records, fim, F, S, sh, ra->anti_aliasing, images, ra->halo); break;
-                case 2: nr_launch(k_shade_px<2>, grid, dim3(256), 0, st, face_records, fim, F, S, sh, ra->anti_aliasing, images, ra->halo); break;
-                default: nr_launch(k_shade_px<3>, grid, dim3(256), 0, st, face_records, fim, F, S, sh, ra->anti_aliasing, images, ra->halo); break;
-            }
-            return check_launch("k_shade");
-        }
-        const dim3 grid((unsigned)(((long long)s * s + 255) / 256), B);
-        switch ((sh.nl ? 1 : 0) | (sh.bg ? 2 : 0)) {
-            case 0: nr_launch(k_shade<0>, grid, dim3(256), 0, st, face_records, fim, F, S, sh, ra->anti_aliasing, images, ra->halo); break;
-            case 1: nr_launch(k_shade<1>, grid, dim3(256), 0, st, face_records, fim, F, S, sh, ra->anti_aliasing, images, ra->halo); break;
-            case 2: nr_launch(k_shade<2>, grid, dim3(256), 0, st, face_records, fim, F, S, sh, ra->anti_aliasing, images, ra->halo); break;
-            default: nr_launch(k_shade<3>, grid, dim3(256), 0, st, face_records, fim, F, S, sh, ra->anti_aliasing, images, ra->halo); break;
-        }
+        nr_launch(shade_kernel(small, (sh.nl ? 1 : 0) | (sh.bg ? 2 : 0)),
+                  dim3((unsigned)(((long long)s * s + per_block - 1) / per_block), B), dim3(256), 0, st, face_records, fim,
+                  F, S, sh, ra->anti_aliasing, images, ra->halo);
     }
     return check_launch("k_shade");
 }
@@ -629,14 +610,7 @@ int nr_rasterize_backward(const NrRasterArgs* a, const float* grad_images, float
     // (up to 16 texels per thread: the car's texture-gradient output rides on its k_vertex_grad blocks,
     // 0.022 + 0.0135 -> 0.031 ms; at 8 it had a launch of its own; same-box A/B, gpurun_out/o28)
     const bool carry = nv > 0 && to.n <= 16 * vgrad_threads;
-#ifdef NR_ABL_EXTRAK
-    nr_launch(k_abl_empty, dim3(NR_ABL_EXTRAK), dim3(256), 0, st, 0);
-#endif
-#ifdef NR_ABL_NOVGRAD
-    if (false) {
-#else
     if (nv > 0) {
-#endif
         {
             ProfScope _p(P_VGRAD, st, true);
             nr_launch(k_vertex_grad, dim3((unsigned)vblocks), dim3(VB), 0, st, gF, a->vertex_offsets,
@@ -689,15 +663,10 @@ int nr_rasterize_backward_params(const NrRasterArgs* a, const float* grad_images
     ba.s = a->image_size;
     const Shade sh = make_shade(a);  // the lights shade (cw) the uv gradient even without light gradients
     const dim3 grid((unsigned)(((long long)S * S + 255) / 256), B);
-    if (uv && lgt)
-        nr_launch((k_param_bwd<true, true>), grid, dim3(256), 0, st, ba, sh, S, a->faces_textures,
-                           grad_vertices_textures, gvt_bstride, grad_lights);
-    else if (uv)
-        nr_launch((k_param_bwd<true, false>), grid, dim3(256), 0, st, ba, sh, S, a->faces_textures,
-                           grad_vertices_textures, gvt_bstride, grad_lights);
-    else
-        nr_launch((k_param_bwd<false, true>), grid, dim3(256), 0, st, ba, sh, S, a->faces_textures,
-                           grad_vertices_textures, gvt_bstride, grad_lights);
+    auto kernel = k_param_bwd<true, true>;  // <UV, LGT>: at least one of the two is wanted here
+    if (!lgt) kernel = k_param_bwd<true, false>;
+    if (!uv) kernel = k_param_bwd<false, true>;
+    nr_launch(kernel, grid, dim3(256), 0, st, ba, sh, S, a->faces_textures, grad_vertices_textures, gvt_bstride, grad_lights);
     return check_launch("k_param_bwd");
 }
 

@@ -366,7 +366,7 @@ def test_face_index_deep_stack_depth_cull(oracle_mod, dev, zlevels):
 
 @pytest.mark.parametrize("B", [1, 8])
 def test_quadrant_split_over_cap_vs_oracle(oracle_mod, dev, B):
-    """More deep bins per deep-first list than the quadrant split takes (NR_QS_CAP = 16): the deepest
+    """More deep bins per deep-first list than the quadrant split takes (QS_CAP = 16): the deepest
     16 of each list are walked by four quadrant blocks each (ordered_bin part 3), the rest by one
     block with dealt quarters, and every quarter walk takes four faces per step (walk_quarter4); one
     list (B = 1, fused silhouettes + depth) and one list per XCD (B = 8, the face-index map alone, a
@@ -480,6 +480,59 @@ def test_split_forward_from_exiting_threads(dev):
     for img, fim, flags in got:
         assert flags & _lib.NR_LAUNCH_SPLIT
         assert torch.equal(img, want[0]) and torch.equal(fim, want[1])
+
+
+@pytest.mark.gpu
+def test_split_forward_first_call_inside_capture(dev):
+    """A forward that wants to split (fused, anti-aliased, deep-first, B % 8 == 0) but gets no side
+    stream: a thread's side stream is created on its first split forward outside a stream capture, so
+    the first forward of a fresh thread, made inside a capture, does not split.  It runs the
+    dealt-quarter kernel with quadrant blocks over its eight lists and reads the dense masks the setup
+    wrote for the split.  Every bin holds >= 512 candidates and Bcap = 8 <= B.  The replayed image and
+    face-index map equal the eager split forward's bit for bit."""
+    import threading
+    r = np.random.RandomState(12)
+    S, F, B = 64, 4000, 8
+    cx = r.uniform(-0.9, 0.9, size=(B, F, 1))
+    cy = r.uniform(-0.9, 0.9, size=(B, F, 1))
+    x = (cx + r.uniform(-0.12, 0.12, size=(B, F, 3))).astype(np.float32)
+    y = (cy + r.uniform(-0.12, 0.12, size=(B, F, 3))).astype(np.float32)
+    z = r.uniform(0.5, 5.0, size=(B, F, 3)).astype(np.float32)
+    verts = torch.as_tensor(np.stack([x, y, z], -1).reshape(B, F * 3, 3), device=dev)
+    faces = torch.arange(F * 3, dtype=torch.int32, device=dev).reshape(F, 3)
+
+    def render():
+        hp = nr.RasterizeHyperparam(image_size=S // 2, anti_aliasing=True)
+        hp.draw_rgb = False
+        return nrr.rasterize_core(verts, faces, nr.RasterizeParam(), hp, return_face_index=True)
+
+    img, fim = render()
+    ntf, flags = _lib.last_launch("k_raster_fwd")
+    torch.cuda.synchronize()
+    assert ntf == 1024 and flags & _lib.NR_LAUNCH_SPLIT, (ntf, flags)
+    want = img.cpu(), fim.cpu()
+    got = {}
+
+    def captured():
+        try:
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                gimg, gfim = render()
+            got["launch"] = _lib.last_launch("k_raster_fwd")
+            graph.replay()
+            torch.cuda.synchronize()
+            got["img"], got["fim"] = gimg.cpu(), gfim.cpu()
+        except BaseException as exc:  # reported by the asserting thread
+            got["error"] = exc
+
+    th = threading.Thread(target=captured)
+    th.start()
+    th.join()
+    assert "error" not in got, repr(got.get("error"))
+    ntf, flags = got["launch"]
+    assert ntf == 1024 and flags & _lib.NR_LAUNCH_QUADRANTS and not flags & _lib.NR_LAUNCH_SPLIT, (ntf, flags)
+    assert torch.equal(got["fim"], want[1]), int((got["fim"] != want[1]).sum())
+    assert torch.equal(got["img"], want[0])
 
 
 def test_headline_properties(dev):

@@ -1,6 +1,9 @@
 # usage: bash tools/car_tex_probe.sh <tag> <lib>...: the car's (cfg3) HBM reads and L2 hit rate per kernel for
-# each library (e.g. the product and the NR_ABL_NOTEX timing build, whose texture samples load no texel):
-# how much of the forward's reads and L2 misses the shared texture atlas causes.  One FETCH_SIZE pass and
+# each library (e.g. the product and a build whose texture samples load no texel): how much of the
+# forward's reads and L2 misses the shared texture atlas causes.  The sources no longer carry a switch
+# for that build; DESIGN.md section 4 names the last commit that has it (build that revision with
+# tools/build_rev.sh and HIPFLAGS holding the product's flags plus the define, and pass the library
+# here as tools/ablate.sh takes its "lib:" variants).  One FETCH_SIZE pass and
 # one TCC_HIT / TCC_MISS pass per library, each under its own time limit.
 set -o pipefail
 cd $GRAFT_REPO_ROOT

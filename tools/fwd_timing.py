@@ -76,7 +76,7 @@ if split:
     parts = [("deep launch (1024 threads)", raw[:nbins * bcap * 16 * 10].reshape(nbins * bcap, 16, 10)),
              ("rest launch (256 threads, side stream)", raw[HALF:HALF + nbins * batch * 4 * 10].reshape(nbins * batch, 4, 10))]
 else:
-    # (a deep-first forward that does not split launches 3 x 16 (NR_QS_CAP) quadrant blocks per list beyond its bins)
+    # (a deep-first forward that does not split launches 3 x 16 (QS_CAP, nr_raster.hip) quadrant blocks per list beyond its bins)
     nblk = nbins * batch + (3 * 16 * (8 if batch % 8 == 0 else 1) if flags & _lib.NR_LAUNCH_QUADRANTS else 0)
     parts = [("k_raster_fwd<%d>" % threads, raw[:nblk * waves * 10].reshape(nblk, waves, 10))]
 # blocks past their launch's part of the deep-first list return before their first stamp
