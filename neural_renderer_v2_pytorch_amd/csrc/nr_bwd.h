@@ -877,7 +877,9 @@ __global__ __launch_bounds__(64) void k_hot_reduce(const float* __restrict__ acc
 template <int FEAT, bool HOT>
 void launch_bwd_v(dim3 grid, hipStream_t st, const BwdArgs& ba, const Geom& g, const Shade& sh) {
     const bool one = (long long)grid.x * grid.y < 8192;
-    const int hotf = HOT ? NR_LAUNCH_HOT_WINDOWS : 0;
+    // the record's constant bits: the shared-window flush and the feature instantiation
+    const int hotf = (HOT ? NR_LAUNCH_HOT_WINDOWS : 0) | ((FEAT & 1) ? NR_LAUNCH_LIGHTS : 0) |
+                     ((FEAT & 2) ? NR_LAUNCH_BACKGROUNDS : 0) | ((FEAT & 4) ? NR_LAUNCH_SIL_ONLY : 0);
     if (one) {
         nr_launch((k_raster_bwd<FEAT, 1, 0, HOT>), grid, dim3(2 * NT), 0, st, ba, g, sh);
         g_last_bwd.store(LaunchRec{2 * NT, hotf});

@@ -627,15 +627,18 @@ def test_headline_full_batch_vs_oracle(oracle_mod, dev):
     close_grads(leaf.grad, rgt, "shared texture gradient (sum over 64 items)")
 
 
-def test_sparse_face_index_forward_vs_oracle(oracle_mod, dev):
+@pytest.mark.parametrize("B", [8, 16])
+def test_sparse_face_index_forward_vs_oracle(oracle_mod, dev, B):
     """The forward whose face-index map stays internal (return_face_index=False, halo cache on)
     leaves the -1 entries of bins without candidate faces unwritten (NrRasterArgs.face_index_sparse);
     the backward must read none of them.  The map is filled with face id 0 before the forward, so a
     read of an unwritten entry would add face 0's gradient at a background pixel: images and
     gradients of 8 headline items (ico 5120, 256^2 AA, rgb + sil + depth, shared texture) against
-    the oracle, and against the same render with the full map (return_face_index=True)."""
-    B = 8
-    proj, f = _ico_batch(4, B, dev)
+    the oracle, and against the same render with the full map (return_face_index=True).  B = 16
+    (ico 1280, so that the oracle takes no longer than for the 8 items) is 8192 backward blocks: the
+    2-pixel-per-lane backward with compile-time channels, the one the headline bench runs on its
+    sparse map (asserted from the launch record)."""
+    proj, f = _ico_batch(4 if B == 8 else 3, B, dev)
     vt, ft, tex = nr.create_textures(f.shape[0], texture_size=4)
     tex_cpu = torch.rand(tex.shape, generator=torch.Generator().manual_seed(5))
     g = torch.randn((B, 5, 256, 256), generator=torch.Generator().manual_seed(6))
@@ -655,6 +658,10 @@ def test_sparse_face_index_forward_vs_oracle(oracle_mod, dev):
         if want_fim:
             img = img[0]
         img.backward(g.to(dev))
+        if B == 16:
+            torch.cuda.synchronize()
+            assert _lib.last_launch("k_raster_bwd") == (256, _lib.NR_LAUNCH_STATIC_CHANNELS |
+                                                        _lib.NR_LAUNCH_TWO_PX_PER_LANE)
         out[want_fim] = (img.detach(), pv.grad, leaf.grad)
     assert torch.equal(out[False][0], out[True][0])
     ref, rfim, rgv, rgt = oracle_batch(oracle_mod, proj, f, g, 256, tex_cpu, vt, ft)
