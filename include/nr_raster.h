@@ -239,7 +239,9 @@ NR_API int nr_rasterize_backward_params(const NrRasterArgs* args, const float* g
  * the default at = (0, 0, 0) / up = (0, 1, 0) or the given ones) and/or perspective
  * (perspective.py:4-18), fused.  Cross products are per item (the reference's dim-less torch.cross
  * mixes items at B == 3, SURVEY section 8a hazards). */
-enum { NR_CAMERA_NONE = 0, NR_CAMERA_LOOK_AT = 1 };
+/* NR_CAMERA_LOOK (look.py:5-30): the camera looks along a fixed direction, carried in `at` (z_u = at);
+ * the axes then do not depend on the eye, whose gradient is the translation term alone. */
+enum { NR_CAMERA_NONE = 0, NR_CAMERA_LOOK_AT = 1, NR_CAMERA_LOOK = 2 };
 typedef struct NrCameraArgs {
     int batch_size;            /* B */
     int num_vertices;          /* V */
@@ -248,8 +250,8 @@ typedef struct NrCameraArgs {
     const float* eye;          /* [B, 3] viewpoints; eye_batch_stride 0 = one eye for every item */
     long long eye_batch_stride;
     int mode;                  /* NR_CAMERA_* */
-    float at[3], up[3];
-    int perspective;           /* apply x / z / width, y / z / width */
+    float at[3], up[3];        /* at: the point looked at (LOOK_AT) or the viewing direction (LOOK) */
+    int perspective;          /* apply x / z / width, y / z / width */
     float width;               /* tan(angle / 180 * 3.1416) in f32, as perspective.py:10-13 computes it */
 } NrCameraArgs;
 
@@ -262,6 +264,47 @@ NR_API size_t nr_camera_workspace_bytes(int batch_size);
  * given are fully written. */
 NR_API int nr_camera_backward(const NrCameraArgs* args, const float* grad_out, float* grad_vertices,
                               float* grad_eye, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Calibrated camera (projection.py): per vertex v of item b
+ *   p = R v + t = (x, y, z);  x' = x / (z + eps), y' = y / (z + eps), r2 = x'^2 + y'^2
+ *   rad = 1 + k1 r2 + k2 r2^2 + k3 r2^3
+ *   x'' = x' rad + 2 p1 x' y' + p2 (r2 + 2 x'^2);  y'' = y' rad + p1 (r2 + 2 y'^2) + 2 p2 x' y'
+ *   u = K00 x'' + K01 y'' + K02;  v = K10 x'' + K11 y'' + K12          (row 2 of K is not read)
+ *   out = (2 (u - S/2) / S, 2 ((S - v) - S/2) / S, z)                  with S = orig_size
+ * dist holds (k1, k2, p1, p2, k3) per item, in OpenCV's order.  Batch strides are in elements; 0 = the
+ * one record is shared by every item. */
+typedef struct NrProjectionArgs {
+    int batch_size;            /* B */
+    int num_vertices;          /* V */
+    const float* vertices;     /* [B, V, 3] world space; v_batch_stride 0 = one mesh for every item */
+    long long v_batch_stride;
+    const float* K;            /* [B, 3, 3] row-major intrinsics */
+    long long k_batch_stride;
+    const float* R;            /* [B, 3, 3] row-major rotation */
+    long long r_batch_stride;
+    const float* t;            /* [B, 3] translation */
+    long long t_batch_stride;
+    const float* dist;         /* [B, 5] distortion coefficients, or NULL = zeros */
+    long long dist_batch_stride;
+    float orig_size;           /* S */
+    float eps;
+} NrProjectionArgs;
+
+/* sizeof(NrProjectionArgs), for bindings to check their mirror of the struct */
+NR_API size_t nr_projection_args_size(void);
+/* out [B, V, 3] contiguous. */
+NR_API int nr_projection_forward(const NrProjectionArgs* args, float* out, void* stream);
+/* Scratch bytes of nr_projection_backward when a parameter gradient is asked for: the per-block partial
+ * sums [B][ceil(V / 256)][24] (no zero fill needed; every entry read is written first). */
+NR_API size_t nr_projection_workspace_bytes(int batch_size, int num_vertices);
+/* grad_out [B, V, 3] -> grad_vertices [Bv, V, 3], grad_K [Bk, 3, 3] (row 2 zero), grad_R [Br, 3, 3],
+ * grad_t [Bt, 3], grad_dist [Bd, 5], each with Bx = (its batch stride ? B : 1), the item sum when shared.
+ * Any of them may be NULL; those given are fully written (zeros when B == 0 or V == 0).  The parameter
+ * gradients are summed in a fixed order without atomics: bitwise reproducible from run to run.  The
+ * workspace is needed only with a parameter gradient. */
+NR_API int nr_projection_backward(const NrProjectionArgs* args, const float* grad_out, float* grad_vertices,
+                                  float* grad_K, float* grad_R, float* grad_t, float* grad_dist,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /* Diagnostics (no reference counterpart): the kernels replace some IEEE divisions by a shortened
  * form of the compiler's own division sequence inside a guarded operand range (DESIGN.md,

@@ -9,12 +9,13 @@ from .load_obj import load_obj
 from .look import look
 from .look_at import look_at
 from .perspective import perspective
+from .projection import projection
 from .rasterize import rasterize_core, rasterize_depth, rasterize_rgb, rasterize_rgba, rasterize_silhouettes
 from .rasterize_param import RasterizeHyperparam, RasterizeParam
 from .renderer import Renderer
 from .save_obj import save_obj
 from .utils import create_textures, get_points_from_angles, imread, make_gif, to_gpu
 from .differentiation import differentiation
-from .camera import camera_transform
+from .camera import camera_transform, projection_transform
 
 __version__ = '2.0.2+mi355x.1'

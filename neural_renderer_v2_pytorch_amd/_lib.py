@@ -26,6 +26,7 @@ EXPORTS = [
     "nr_selftest_division", "nr_halo_bytes", "nr_raster_args_size", "nr_rasterize_backward_params",
     "nr_camera_forward", "nr_camera_backward", "nr_camera_workspace_bytes", "nr_texture_packed_bytes",
     "nr_last_launch", "nr_hot_acc_bytes",
+    "nr_projection_args_size", "nr_projection_forward", "nr_projection_workspace_bytes", "nr_projection_backward",
 ]
 
 ABI_VERSION = 6  # include/nr_raster.h NR_ABI_VERSION
@@ -60,7 +61,7 @@ class NrRasterArgs(ctypes.Structure):
     ]
 
 NR_LIGHT_AMBIENT, NR_LIGHT_DIRECTIONAL, NR_LIGHT_SPECULAR, NR_LIGHT_FLOATS = 0, 1, 2, 8
-NR_CAMERA_NONE, NR_CAMERA_LOOK_AT = 0, 1
+NR_CAMERA_NONE, NR_CAMERA_LOOK_AT, NR_CAMERA_LOOK = 0, 1, 2
 
 
 class NrCameraArgs(ctypes.Structure):  # include/nr_raster.h
@@ -68,6 +69,15 @@ class NrCameraArgs(ctypes.Structure):  # include/nr_raster.h
         ("batch_size", c_int), ("num_vertices", c_int), ("vertices", c_void_p), ("v_batch_stride", c_ll),
         ("eye", c_void_p), ("eye_batch_stride", c_ll), ("mode", c_int), ("at", c_float * 3), ("up", c_float * 3),
         ("perspective", c_int), ("width", c_float),
+    ]
+
+
+class NrProjectionArgs(ctypes.Structure):  # include/nr_raster.h
+    _fields_ = [
+        ("batch_size", c_int), ("num_vertices", c_int), ("vertices", c_void_p), ("v_batch_stride", c_ll),
+        ("K", c_void_p), ("k_batch_stride", c_ll), ("R", c_void_p), ("r_batch_stride", c_ll),
+        ("t", c_void_p), ("t_batch_stride", c_ll), ("dist", c_void_p), ("dist_batch_stride", c_ll),
+        ("orig_size", c_float), ("eps", c_float),
     ]
 
 
@@ -82,6 +92,12 @@ def lib():
         raise RuntimeError("neural_renderer_v2_pytorch_amd: HIP library %s is missing; build it with "
                            "__graft_entry__.build() (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
+    # additions within one ABI version (the nr_projection_* entry points): a library built before them
+    # still reports the version this binding expects
+    missing = [name for name in EXPORTS if not hasattr(L, name)]
+    if missing:
+        raise RuntimeError("neural_renderer_v2_pytorch_amd: %s lacks %s; this binding needs a newer build of the "
+                           "library (rebuild with __graft_entry__.build())" % (LIB_PATH, ", ".join(missing)))
     L.nr_last_error.restype = ctypes.c_char_p
     L.nr_last_error.argtypes = []
     L.nr_version.restype = c_int
@@ -106,6 +122,13 @@ def lib():
     L.nr_texture_packed_bytes.argtypes = [c_int, c_int, c_int]
     L.nr_camera_workspace_bytes.restype = c_size_t
     L.nr_camera_workspace_bytes.argtypes = [c_int]
+    L.nr_projection_args_size.restype = c_size_t
+    L.nr_projection_args_size.argtypes = []
+    L.nr_projection_workspace_bytes.restype = c_size_t
+    L.nr_projection_workspace_bytes.argtypes = [c_int, c_int]
+    L.nr_projection_forward.argtypes = [ctypes.POINTER(NrProjectionArgs), c_void_p, c_void_p]
+    L.nr_projection_backward.argtypes = [ctypes.POINTER(NrProjectionArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]
     L.nr_backward_workspace_bytes.restype = c_size_t
     L.nr_backward_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int]
     L.nr_raster_args_size.restype = c_size_t
@@ -121,10 +144,15 @@ def lib():
     for name in EXPORTS:
         if name not in ("nr_last_error", "nr_workspace_bytes", "nr_num_channels", "nr_backward_workspace_bytes",
                         "nr_halo_bytes", "nr_raster_args_size", "nr_camera_workspace_bytes",
-                        "nr_texture_packed_bytes", "nr_hot_acc_bytes"):
+                        "nr_texture_packed_bytes", "nr_hot_acc_bytes", "nr_projection_args_size",
+                        "nr_projection_workspace_bytes"):
             getattr(L, name).restype = c_int
     # a library of another ABI revision (an NR_LIB_PATH override, a stale build) would misread the
     # arguments (e.g. an older nr_rasterize_backward takes its stream where workspace_zeroed is now)
+    if L.nr_projection_args_size() != ctypes.sizeof(NrProjectionArgs):
+        raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has a %d-byte NrProjectionArgs; this binding needs %d "
+                           "bytes (rebuild with __graft_entry__.build())"
+                           % (LIB_PATH, L.nr_projection_args_size(), ctypes.sizeof(NrProjectionArgs)))
     if L.nr_version() != ABI_VERSION or L.nr_raster_args_size() != ctypes.sizeof(NrRasterArgs):
         raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has ABI version %d with a %d-byte NrRasterArgs; this "
                            "binding needs version %d and %d bytes (rebuild with __graft_entry__.build())"

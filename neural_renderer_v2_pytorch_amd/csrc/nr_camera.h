@@ -1,4 +1,4 @@
-// nr_camera.h -- camera prologue (look_at + perspective) forward and backward kernels
+// nr_camera.h -- camera prologue (look_at / look + perspective) forward and backward kernels
 // Part of nr_raster.hip (one translation unit); see that file and DESIGN.md.
 #pragma once
 
@@ -27,11 +27,11 @@ __device__ __forceinline__ void cam_cross(const float a[3], const float b[3], fl
     o[1] = a[2] * b[0] - a[0] * b[2];
     o[2] = a[0] * b[1] - a[1] * b[0];
 }
-// the look_at axes for eye e (cross products per item: the reference's dim-less torch.cross crosses
+// the look_at axes for eye e, or the look axes along the direction c.at (cross products per item: the reference's dim-less torch.cross crosses
 // along the batch axis at B == 3, a hazard not replicated)
 __device__ __forceinline__ void cam_build(const NrCameraArgs& c, const float e[3], Cam& m) {
 #pragma unroll
-    for (int j = 0; j < 3; j++) m.z_u[j] = c.at[j] - e[j];
+    for (int j = 0; j < 3; j++) m.z_u[j] = c.mode == NR_CAMERA_LOOK ? c.at[j] : c.at[j] - e[j];
     cam_normalize(m.z_u, m.r[2]);
     cam_cross(c.up, m.r[2], m.x_u);
     cam_normalize(m.x_u, m.r[0]);
@@ -62,7 +62,7 @@ __global__ void k_camera_fwd(NrCameraArgs c, float* __restrict__ out) {
     const int b = (int)(i / c.num_vertices), v = (int)(i - (long long)b * c.num_vertices);
     const float* vp = c.vertices + (long long)b * c.v_batch_stride + v * 3;
     float p[3] = {vp[0], vp[1], vp[2]};
-    if (c.mode == NR_CAMERA_LOOK_AT) {
+    if (c.mode != NR_CAMERA_NONE) {
         float e[3];
         cam_eye(c, b, e);
         Cam m;
@@ -86,9 +86,9 @@ __device__ __forceinline__ void cam_point_bwd(const NrCameraArgs& c, const float
     const float* vp = c.vertices + (long long)b * c.v_batch_stride + v * 3;
     const float* g = go + ((long long)b * c.num_vertices + v) * 3;
     d[0] = vp[0], d[1] = vp[1], d[2] = vp[2];
-    if (c.mode == NR_CAMERA_LOOK_AT) d[0] -= e[0], d[1] -= e[1], d[2] -= e[2];
+    if (c.mode != NR_CAMERA_NONE) d[0] -= e[0], d[1] -= e[1], d[2] -= e[2];
     float q[3] = {d[0], d[1], d[2]};
-    if (c.mode == NR_CAMERA_LOOK_AT) {
+    if (c.mode != NR_CAMERA_NONE) {
 #pragma unroll
         for (int k = 0; k < 3; k++) q[k] = (d[0] * m.r[k][0] + d[1] * m.r[k][1]) + d[2] * m.r[k][2];
     }
@@ -115,20 +115,20 @@ __global__ void k_camera_bwd(NrCameraArgs c, const float* __restrict__ go, float
         const int b = shared ? bb : b0;
         float e[3] = {0.f, 0.f, 0.f};
         Cam m;
-        if (c.mode == NR_CAMERA_LOOK_AT) {
+        if (c.mode != NR_CAMERA_NONE) {
             cam_eye(c, b, e);
             cam_build(c, e, m);
         }
         float gq[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
         if (live) cam_point_bwd(c, go, b, v, m, e, gq, d);
-        if (c.mode == NR_CAMERA_LOOK_AT) {
+        if (c.mode != NR_CAMERA_NONE) {
 #pragma unroll
             for (int j = 0; j < 3; j++) out[j] += (gq[0] * m.r[0][j] + gq[1] * m.r[1][j]) + gq[2] * m.r[2][j];
         } else {
 #pragma unroll
             for (int j = 0; j < 3; j++) out[j] += gq[j];
         }
-        if (acc && c.mode == NR_CAMERA_LOOK_AT) {
+        if (acc && c.mode != NR_CAMERA_NONE) {
             // items differ across a wave only at item boundaries (shared meshes loop over b uniformly)
             const int bl = __builtin_amdgcn_readfirstlane(b);
             const bool same = __builtin_amdgcn_ballot_w64(b != bl) == 0ull;
@@ -160,8 +160,8 @@ __global__ void k_camera_bwd(NrCameraArgs c, const float* __restrict__ go, float
 }
 
 // eye gradient per item from acc = (s = sum g', M = sum g' (v - eye)^T): the translation gives -R^T s,
-// the rotation rows get dR = M and go back through normalize / cross to z_u = at - eye.  A shared eye
-// (batch stride 0) sums its items in order.
+// the rotation rows get dR = M and go back through normalize / cross to z_u = at - eye (look_at only:
+// look's z_u is the constant direction).  A shared eye (batch stride 0) sums its items in order.
 __global__ void k_camera_eye(NrCameraArgs c, const float* __restrict__ acc, float* __restrict__ ge) {
     const bool shared = c.eye_batch_stride == 0;
     const int n = shared ? 1 : c.batch_size;
@@ -175,6 +175,11 @@ __global__ void k_camera_eye(NrCameraArgs c, const float* __restrict__ acc, floa
         cam_eye(c, b, e);
         Cam m;
         cam_build(c, e, m);
+        if (c.mode == NR_CAMERA_LOOK) {  // the axes do not depend on the eye: the translation term alone
+#pragma unroll
+            for (int j = 0; j < 3; j++) tot[j] += -((A[0] * m.r[0][j] + A[1] * m.r[1][j]) + A[2] * m.r[2][j]);
+            continue;
+        }
         float gr[3][3];
 #pragma unroll
         for (int k = 0; k < 3; k++)

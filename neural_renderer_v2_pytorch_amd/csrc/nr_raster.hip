@@ -23,8 +23,8 @@
 //
 // Source layout (one translation unit): nr_common.h (errors, profiling, geometry, exact division,
 // per-pixel shading, XCD tile map), nr_fwd.h (setup + face-index raster), nr_shade.h (image epilogue,
-// halo cache, standalone reference kernels), nr_bwd.h (backward), nr_camera.h (look_at + perspective),
-// nr_host.h (argument checks); this file holds the extern "C" ABI.
+// halo cache, standalone reference kernels), nr_bwd.h (backward), nr_camera.h (look_at / look +
+// perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_host.h (argument checks); this file holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -50,6 +50,7 @@
 #include "nr_fwd.h"
 #include "nr_bwd.h"
 #include "nr_camera.h"
+#include "nr_projection.h"
 #include "nr_host.h"
 
 
@@ -673,9 +674,9 @@ int nr_rasterize_backward_params(const NrRasterArgs* a, const float* grad_images
 static int validate_camera(const NrCameraArgs* c) {
     if (!c) return fail(NR_ERR_ARGS, "null camera args");
     if (c->batch_size < 0 || c->num_vertices < 0) return fail(NR_ERR_ARGS, "bad sizes B=%d V=%d", c->batch_size, c->num_vertices);
-    if (c->mode != NR_CAMERA_NONE && c->mode != NR_CAMERA_LOOK_AT) return fail(NR_ERR_ARGS, "bad camera mode %d", c->mode);
+    if (c->mode != NR_CAMERA_NONE && c->mode != NR_CAMERA_LOOK_AT && c->mode != NR_CAMERA_LOOK) return fail(NR_ERR_ARGS, "bad camera mode %d", c->mode);
     if ((long long)c->batch_size * c->num_vertices > 0 && !c->vertices) return fail(NR_ERR_ARGS, "null vertices");
-    if (c->mode == NR_CAMERA_LOOK_AT && c->batch_size > 0 && !c->eye) return fail(NR_ERR_ARGS, "null eye");
+    if (c->mode != NR_CAMERA_NONE && c->batch_size > 0 && !c->eye) return fail(NR_ERR_ARGS, "null eye");
     return NR_OK;
 }
 
@@ -696,7 +697,7 @@ int nr_camera_backward(const NrCameraArgs* c, const float* grad_out, float* grad
     int e = validate_camera(c);
     if (e) return e;
     hipStream_t st = (hipStream_t)stream;
-    const bool want_eye = grad_eye && c->mode == NR_CAMERA_LOOK_AT;
+    const bool want_eye = grad_eye && c->mode != NR_CAMERA_NONE;
     const int neye = c->eye_batch_stride ? c->batch_size : 1;
     if (grad_eye && !want_eye) {  // no eye in the transform: zero gradient
         if (hipMemsetAsync(grad_eye, 0, (size_t)neye * 3 * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");
@@ -728,6 +729,74 @@ int nr_camera_backward(const NrCameraArgs* c, const float* grad_out, float* grad
         e = check_launch("k_camera_eye");
     }
     return e;
+}
+
+size_t nr_projection_args_size(void) { return sizeof(NrProjectionArgs); }
+
+static int proj_blocks(int num_vertices) { return (int)(((long long)num_vertices + PROJ_BLOCK - 1) / PROJ_BLOCK); }
+
+static int validate_projection(const NrProjectionArgs* p) {
+    if (!p) return fail(NR_ERR_ARGS, "null projection args");
+    if (p->batch_size < 0 || p->num_vertices < 0) return fail(NR_ERR_ARGS, "bad sizes B=%d V=%d", p->batch_size, p->num_vertices);
+    if (p->v_batch_stride < 0 || p->k_batch_stride < 0 || p->r_batch_stride < 0 || p->t_batch_stride < 0 ||
+        p->dist_batch_stride < 0)
+        return fail(NR_ERR_ARGS, "negative batch stride");
+    if (p->batch_size == 0 || p->num_vertices == 0) return NR_OK;
+    if (!p->vertices) return fail(NR_ERR_ARGS, "null vertices");
+    if (!p->K || !p->R || !p->t) return fail(NR_ERR_ARGS, "null K, R or t");
+    if (!(p->orig_size > 0.f) || !(p->orig_size < INFINITY)) return fail(NR_ERR_ARGS, "bad orig_size %g", (double)p->orig_size);
+    if ((long long)p->batch_size * proj_blocks(p->num_vertices) > INT_MAX)
+        return fail(NR_ERR_ARGS, "too many vertices B=%d V=%d", p->batch_size, p->num_vertices);
+    return NR_OK;
+}
+
+size_t nr_projection_workspace_bytes(int batch_size, int num_vertices) {
+    if (batch_size <= 0 || num_vertices <= 0) return 0;
+    return align_up((size_t)batch_size * proj_blocks(num_vertices) * PROJ_SLOT * 4);
+}
+
+int nr_projection_forward(const NrProjectionArgs* p, float* out, void* stream) {
+    int e = validate_projection(p);
+    if (e) return e;
+    if (p->batch_size == 0 || p->num_vertices == 0) return NR_OK;
+    if (!out) return fail(NR_ERR_ARGS, "null output");
+    const int nblk = proj_blocks(p->num_vertices);
+    nr_launch(k_proj_fwd, dim3((unsigned)(p->batch_size * nblk)), dim3(PROJ_BLOCK), 0, (hipStream_t)stream, *p, nblk, out);
+    return check_launch("k_proj_fwd");
+}
+
+int nr_projection_backward(const NrProjectionArgs* p, const float* grad_out, float* grad_vertices, float* grad_K,
+                           float* grad_R, float* grad_t, float* grad_dist, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+    int e = validate_projection(p);
+    if (e) return e;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = p->batch_size, V = p->num_vertices;
+    if (B == 0 || V == 0) {  // nothing projected: zero gradients
+        const struct { float* g; size_t n; } fill[5] = {
+            {grad_vertices, (size_t)(p->v_batch_stride ? B : 1) * V * 3}, {grad_K, (size_t)(p->k_batch_stride ? B : 1) * 9},
+            {grad_R, (size_t)(p->r_batch_stride ? B : 1) * 9},           {grad_t, (size_t)(p->t_batch_stride ? B : 1) * 3},
+            {grad_dist, (size_t)(p->dist_batch_stride ? B : 1) * 5}};
+        for (const auto& f : fill)
+            if (f.g && f.n && hipMemsetAsync(f.g, 0, f.n * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");
+        return NR_OK;
+    }
+    const bool params = grad_K || grad_R || grad_t || grad_dist;
+    if (!grad_vertices && !params) return NR_OK;
+    if (!grad_out) return fail(NR_ERR_ARGS, "null grad_out");
+    if (params && (!workspace || workspace_bytes < nr_projection_workspace_bytes(B, V)))
+        return fail(NR_ERR_WORKSPACE, "projection workspace missing or too small");
+    const int nblk = proj_blocks(V);
+    float* slab = params ? (float*)workspace : nullptr;
+    nr_launch(k_proj_bwd, dim3((unsigned)((p->v_batch_stride ? B : 1) * nblk)), dim3(PROJ_BLOCK), 0, st, *p, nblk, grad_out,
+              grad_vertices, slab);
+    e = check_launch("k_proj_bwd");
+    if (e || !params) return e;
+    const bool per_item = (grad_K && p->k_batch_stride) || (grad_R && p->r_batch_stride) || (grad_t && p->t_batch_stride) ||
+                          (grad_dist && p->dist_batch_stride);
+    nr_launch(k_proj_params, dim3((unsigned)(per_item ? B : 1)), dim3(PROJ_BLOCK), 0, st, *p, nblk, slab, grad_K, grad_R, grad_t,
+              grad_dist);
+    return check_launch("k_proj_params");
 }
 
 int nr_selftest_division(const float* a, const float* b, float* q_fast, float* q_ieee, long long n, void* stream) {

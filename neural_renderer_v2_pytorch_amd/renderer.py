@@ -5,6 +5,7 @@ from . import camera
 from .look import look
 from .look_at import look_at
 from .perspective import perspective
+from .projection import projection
 from .rasterize import rasterize_depth, rasterize_rgb, rasterize_rgba, rasterize_silhouettes
 from .rasterize_param import RasterizeHyperparam, RasterizeParam
 
@@ -24,13 +25,33 @@ class Renderer(object):
         self.camera_direction = [0, 0, 1]
         self.near = 0.1
         self.far = 100
+        # calibrated camera (camera_mode='projection', projection.py)
+        self.K = None
+        self.R = None
+        self.t = None
+        self.dist_coeffs = None
+        self.orig_size = 1024
 
     def transform_vertices(self, vertices, lights=None):
-        # GPU tensors: look_at + perspective fused into one HIP launch each way (camera.py); 'look'
-        # and CPU tensors take the reference's composition of torch ops below
-        if self.camera_mode != 'look' and camera.fusable(vertices, self.viewing_angle):
-            return camera.camera_transform(vertices, self.viewpoints if self.camera_mode == 'look_at' else None,
-                                           perspective=self.perspective, angle=self.viewing_angle)
+        if self.camera_mode == 'projection':
+            # calibrated camera: K, R, t (+ distortion); perspective and viewing_angle are not used
+            for name in ('K', 'R', 't'):
+                if getattr(self, name) is None:
+                    raise ValueError("camera_mode='projection' needs Renderer.%s" % name)
+            args = (vertices, self.K, self.R, self.t, self.dist_coeffs, self.orig_size)
+            if camera.projection_fusable(*args):
+                return camera.projection_transform(*args)
+            return projection(*args)
+        # GPU tensors: look_at / look + perspective fused into one HIP launch each way (camera.py); CPU
+        # tensors, and a 'look' whose direction is per item or takes a gradient, take the reference's
+        # composition of torch ops below
+        if camera.fusable(vertices, self.viewing_angle):
+            if self.camera_mode != 'look':
+                return camera.camera_transform(vertices, self.viewpoints if self.camera_mode == 'look_at' else None,
+                                               perspective=self.perspective, angle=self.viewing_angle)
+            if camera.look_fusable(self.camera_direction):
+                return camera.camera_transform(vertices, self.viewpoints, perspective=self.perspective,
+                                               angle=self.viewing_angle, direction=self.camera_direction)
         if self.camera_mode == 'look_at':
             vertices = look_at(vertices, self.viewpoints)
         elif self.camera_mode == 'look':
