@@ -306,6 +306,45 @@ NR_API int nr_projection_backward(const NrProjectionArgs* args, const float* gra
                                   float* grad_K, float* grad_R, float* grad_t, float* grad_dist,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* Mesh regularizers (mesh_loss.py), for vertices [B, V, 3] contiguous and a topology shared by every item.
+ * No float atomics: losses and gradients are bitwise reproducible from run to run.
+ *
+ * Laplacian: N(i) = the distinct vertices sharing a face edge with i, as the CSR nbr_offsets [V + 1] /
+ * nbr_index (ascending per vertex; symmetric: j in N(i) <=> i in N(j)).
+ *   delta_i = v_i - (1 / |N(i)|) sum_{j in N(i)} v_j   (0 when N(i) is empty);   loss_b = sum_i |delta_i|^2
+ *   grad v_i = 2 g_b (delta_i - sum_{j in N(i)} delta_j / |N(j)|)
+ * Flatten: edges [E2, 4] int32 rows (v0, v1, v2, v3), one per undirected edge v0 < v1 with exactly two
+ * incident faces, v2 / v3 their opposite vertices (16-byte aligned).  Per row, with a = v1 - v0,
+ * b1 = v2 - v0, b2 = v3 - v0:
+ *   c_k = b_k - a (a . b_k) / (|a|^2 + eps);  cos = (c_1 . c_2) / (sqrt(|c_1|^2 + eps) sqrt(|c_2|^2 + eps))
+ *   loss_b = sum_rows (cos + 1)^2
+ * edge_offsets [V + 1] / edge_slots [4 E2]: CSR vertex -> the entries 4 e + k with edges[e, k] == vertex,
+ * ascending.
+ * Limits: 4 E2 < 2^31; B * ceil(V / 256) and B * ceil(E2 / 256) <= INT_MAX (NR_ERR_ARGS otherwise).  The
+ * topology arrays are trusted: every vertex index in them must be below V, every slot below 4 E2.
+ *
+ * Scratch bytes of a forward: the per-block partial sums [B][ceil(count / 256)], count = V (Laplacian) or
+ * E2 (flatten); no zero fill needed. */
+NR_API size_t nr_mesh_loss_workspace_bytes(int batch_size, int count);
+/* loss [B], fully written (0 when V == 0).  delta [B, V, 3] (what the backward reads) or NULL. */
+NR_API int nr_laplacian_forward(const float* vertices, const int32_t* nbr_offsets, const int32_t* nbr_index,
+                                int batch_size, int num_vertices, float* delta, float* loss, void* workspace,
+                                size_t workspace_bytes, void* stream);
+/* grad_loss [B] -> grad_vertices [B, V, 3], fully written, from the forward's delta. */
+NR_API int nr_laplacian_backward(const float* delta, const int32_t* nbr_offsets, const int32_t* nbr_index,
+                                 const float* grad_loss, int batch_size, int num_vertices, float* grad_vertices,
+                                 void* stream);
+/* loss [B], fully written (0 when E2 == 0).  records [B, E2, 12] (what the backward reads) or NULL: each
+ * row's gradient to its four vertices (d loss_row / d v0..v3), 16-byte aligned. */
+NR_API int nr_flatten_forward(const float* vertices, const int32_t* edges, int batch_size, int num_vertices,
+                              int num_edges, float eps, float* records, float* loss, void* workspace,
+                              size_t workspace_bytes, void* stream);
+/* grad_loss [B] -> grad_vertices [B, V, 3], fully written: each vertex sums the forward's records of its
+ * slots in ascending order. */
+NR_API int nr_flatten_backward(const float* records, const int32_t* edge_offsets, const int32_t* edge_slots,
+                               const float* grad_loss, int batch_size, int num_vertices, int num_edges,
+                               float* grad_vertices, void* stream);
+
 /* Diagnostics (no reference counterpart): the kernels replace some IEEE divisions by a shortened
  * form of the compiler's own division sequence inside a guarded operand range (DESIGN.md,
  * "Numerics").  This runs both forms on n operand pairs so tests can check they agree bit for bit. */

@@ -17,5 +17,7 @@ from .save_obj import save_obj
 from .utils import create_textures, get_points_from_angles, imread, make_gif, to_gpu
 from .differentiation import differentiation
 from .camera import camera_transform, projection_transform
+from .mesh_loss import (FlattenLoss, LaplacianLoss, MeshTopology, flatten_loss, flatten_loss_torch, laplacian_loss,
+                        laplacian_loss_torch, mesh_topology)
 
 __version__ = '2.0.2+mi355x.1'

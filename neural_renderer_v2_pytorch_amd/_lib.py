@@ -27,6 +27,8 @@ EXPORTS = [
     "nr_camera_forward", "nr_camera_backward", "nr_camera_workspace_bytes", "nr_texture_packed_bytes",
     "nr_last_launch", "nr_hot_acc_bytes",
     "nr_projection_args_size", "nr_projection_forward", "nr_projection_workspace_bytes", "nr_projection_backward",
+    "nr_mesh_loss_workspace_bytes", "nr_laplacian_forward", "nr_laplacian_backward", "nr_flatten_forward",
+    "nr_flatten_backward",
 ]
 
 ABI_VERSION = 6  # include/nr_raster.h NR_ABI_VERSION
@@ -92,7 +94,7 @@ def lib():
         raise RuntimeError("neural_renderer_v2_pytorch_amd: HIP library %s is missing; build it with "
                            "__graft_entry__.build() (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    # additions within one ABI version (the nr_projection_* entry points): a library built before them
+    # additions within one ABI version (the nr_projection_* and mesh-loss entry points): a library built before them
     # still reports the version this binding expects
     missing = [name for name in EXPORTS if not hasattr(L, name)]
     if missing:
@@ -129,6 +131,14 @@ def lib():
     L.nr_projection_forward.argtypes = [ctypes.POINTER(NrProjectionArgs), c_void_p, c_void_p]
     L.nr_projection_backward.argtypes = [ctypes.POINTER(NrProjectionArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_size_t, c_void_p]
+    L.nr_mesh_loss_workspace_bytes.restype = c_size_t
+    L.nr_mesh_loss_workspace_bytes.argtypes = [c_int, c_int]
+    L.nr_laplacian_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                       c_void_p]
+    L.nr_laplacian_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
+    L.nr_flatten_forward.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
+                                     c_void_p]
+    L.nr_flatten_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
     L.nr_backward_workspace_bytes.restype = c_size_t
     L.nr_backward_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int]
     L.nr_raster_args_size.restype = c_size_t
@@ -145,7 +155,7 @@ def lib():
         if name not in ("nr_last_error", "nr_workspace_bytes", "nr_num_channels", "nr_backward_workspace_bytes",
                         "nr_halo_bytes", "nr_raster_args_size", "nr_camera_workspace_bytes",
                         "nr_texture_packed_bytes", "nr_hot_acc_bytes", "nr_projection_args_size",
-                        "nr_projection_workspace_bytes"):
+                        "nr_projection_workspace_bytes", "nr_mesh_loss_workspace_bytes"):
             getattr(L, name).restype = c_int
     # a library of another ABI revision (an NR_LIB_PATH override, a stale build) would misread the
     # arguments (e.g. an older nr_rasterize_backward takes its stream where workspace_zeroed is now)

@@ -24,7 +24,8 @@
 // Source layout (one translation unit): nr_common.h (errors, profiling, geometry, exact division,
 // per-pixel shading, XCD tile map), nr_fwd.h (setup + face-index raster), nr_shade.h (image epilogue,
 // halo cache, standalone reference kernels), nr_bwd.h (backward), nr_camera.h (look_at / look +
-// perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_host.h (argument checks); this file holds the extern "C" ABI.
+// perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian and
+// flatten regularizers), nr_host.h (argument checks); this file holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -51,6 +52,7 @@
 #include "nr_bwd.h"
 #include "nr_camera.h"
 #include "nr_projection.h"
+#include "nr_mesh_loss.h"
 #include "nr_host.h"
 
 
@@ -797,6 +799,95 @@ int nr_projection_backward(const NrProjectionArgs* p, const float* grad_out, flo
     nr_launch(k_proj_params, dim3((unsigned)(per_item ? B : 1)), dim3(PROJ_BLOCK), 0, st, *p, nblk, slab, grad_K, grad_R, grad_t,
               grad_dist);
     return check_launch("k_proj_params");
+}
+
+// ---- mesh regularizers (nr_mesh_loss.h) ----
+static long long ml_blocks(int count) { return ((long long)count + ML_BLOCK - 1) / ML_BLOCK; }
+
+static int validate_mesh_loss(int B, int V, int E2) {
+    if (B < 0 || V < 0 || E2 < 0) return fail(NR_ERR_ARGS, "bad sizes B=%d V=%d E2=%d", B, V, E2);
+    if (E2 > INT_MAX / 4) return fail(NR_ERR_ARGS, "too many edges E2=%d (4 * E2 must stay below 2^31)", E2);
+    if ((long long)B * ml_blocks(V) > INT_MAX || (long long)B * ml_blocks(E2) > INT_MAX)
+        return fail(NR_ERR_ARGS, "too many vertices or edges B=%d V=%d E2=%d", B, V, E2);
+    return NR_OK;
+}
+
+size_t nr_mesh_loss_workspace_bytes(int batch_size, int count) {
+    if (batch_size <= 0 || count <= 0) return 0;
+    return align_up((size_t)batch_size * (size_t)ml_blocks(count) * 4);
+}
+
+int nr_laplacian_forward(const float* vertices, const int32_t* nbr_offsets, const int32_t* nbr_index, int batch_size,
+                         int num_vertices, float* delta, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+    const int B = batch_size, V = num_vertices;
+    int e = validate_mesh_loss(B, V, 0);
+    if (e) return e;
+    if (B == 0) return NR_OK;
+    if (!loss) return fail(NR_ERR_ARGS, "null loss");
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = (int)ml_blocks(V);
+    if (V > 0) {
+        if (!vertices || !nbr_offsets) return fail(NR_ERR_ARGS, "null vertices or nbr_offsets");
+        if (!workspace || workspace_bytes < nr_mesh_loss_workspace_bytes(B, V))
+            return fail(NR_ERR_WORKSPACE, "mesh loss workspace missing or too small");
+        nr_launch(k_lap_fwd, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, st, vertices, nbr_offsets, nbr_index, V, nblk, delta,
+                  (float*)workspace);
+        e = check_launch("k_lap_fwd");
+        if (e) return e;
+    }
+    nr_launch(k_mesh_loss_sum, dim3((unsigned)B), dim3(ML_BLOCK), 0, st, (const float*)workspace, nblk, loss);
+    return check_launch("k_mesh_loss_sum");
+}
+
+int nr_laplacian_backward(const float* delta, const int32_t* nbr_offsets, const int32_t* nbr_index, const float* grad_loss,
+                          int batch_size, int num_vertices, float* grad_vertices, void* stream) {
+    const int B = batch_size, V = num_vertices;
+    int e = validate_mesh_loss(B, V, 0);
+    if (e) return e;
+    if (B == 0 || V == 0) return NR_OK;
+    if (!delta || !nbr_offsets || !grad_loss || !grad_vertices) return fail(NR_ERR_ARGS, "null pointer");
+    const int nblk = (int)ml_blocks(V);
+    nr_launch(k_lap_bwd, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, (hipStream_t)stream, delta, nbr_offsets, nbr_index,
+              grad_loss, V, nblk, grad_vertices);
+    return check_launch("k_lap_bwd");
+}
+
+int nr_flatten_forward(const float* vertices, const int32_t* edges, int batch_size, int num_vertices, int num_edges, float eps,
+                       float* records, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+    const int B = batch_size, V = num_vertices, E2 = num_edges;
+    int e = validate_mesh_loss(B, V, E2);
+    if (e) return e;
+    if (B == 0) return NR_OK;
+    if (!loss) return fail(NR_ERR_ARGS, "null loss");
+    if (!(eps >= 0.f) || !(eps < INFINITY)) return fail(NR_ERR_ARGS, "bad eps %g", (double)eps);
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = (int)ml_blocks(E2);
+    if (E2 > 0) {
+        if (V == 0 || !vertices || !edges) return fail(NR_ERR_ARGS, "edges without vertices");
+        if (!workspace || workspace_bytes < nr_mesh_loss_workspace_bytes(B, E2))
+            return fail(NR_ERR_WORKSPACE, "mesh loss workspace missing or too small");
+        const dim3 grid((unsigned)(B * nblk));
+        if (records) nr_launch(k_flat_fwd<true>, grid, dim3(ML_BLOCK), 0, st, vertices, edges, V, E2, nblk, eps, records, (float*)workspace);
+        else nr_launch(k_flat_fwd<false>, grid, dim3(ML_BLOCK), 0, st, vertices, edges, V, E2, nblk, eps, records, (float*)workspace);
+        e = check_launch("k_flat_fwd");
+        if (e) return e;
+    }
+    nr_launch(k_mesh_loss_sum, dim3((unsigned)B), dim3(ML_BLOCK), 0, st, (const float*)workspace, nblk, loss);
+    return check_launch("k_mesh_loss_sum");
+}
+
+int nr_flatten_backward(const float* records, const int32_t* edge_offsets, const int32_t* edge_slots, const float* grad_loss,
+                        int batch_size, int num_vertices, int num_edges, float* grad_vertices, void* stream) {
+    const int B = batch_size, V = num_vertices, E2 = num_edges;
+    int e = validate_mesh_loss(B, V, E2);
+    if (e) return e;
+    if (B == 0 || V == 0) return NR_OK;
+    if (!edge_offsets || !grad_loss || !grad_vertices) return fail(NR_ERR_ARGS, "null pointer");
+    if (E2 > 0 && (!edge_slots || !records)) return fail(NR_ERR_ARGS, "null records or edge_slots");
+    const int nblk = (int)ml_blocks(V);
+    nr_launch(k_flat_bwd_gather, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, (hipStream_t)stream, records, edge_offsets,
+              edge_slots, grad_loss, V, E2, nblk, grad_vertices);
+    return check_launch("k_flat_bwd_gather");
 }
 
 int nr_selftest_division(const float* a, const float* b, float* q_fast, float* q_ieee, long long n, void* stream) {
