@@ -652,6 +652,17 @@ __device__ __forceinline__ void shade_pixel(const Shade& sh, int b, int fi, cons
     out[4] = dep;
 }
 
+// n / d of block-uniform n >= 0, d > 0: a shift when d is a power of two.  A runtime 32-bit division
+// is some 30 VALU instructions around a quarter-rate reciprocal (there is no scalar one), and the
+// five of the interleaved map were most of the ~0.5 us life of a backward tile that ends at its bin
+// flag: two thirds of the headline's blocks, which run last and end the kernel (DESIGN section 4
+// "Round 7").  Group sizes and the tile counts of power-of-two rasters take the shifts.  (xcd_tile
+// and ordered_bin keep their divisions: with shifts there the headline gained nothing more and the
+// torus forward measured 1-2 % slower.)
+__device__ __forceinline__ int udiv_uniform(int n, int d) {
+    return (d & (d - 1)) == 0 ? n >> __builtin_ctz(d) : n / d;
+}
+
 // ------------------------------------------------------------------------------------------------
 // XCD-aware block -> tile map.  Workgroups go round-robin to the 8 XCDs (linear id % 8) and each XCD
 // has its own L2, so with the identity map horizontally adjacent tiles never share a cache, and the
@@ -686,15 +697,25 @@ __device__ __forceinline__ int centre_out(int k, int n) {
     const int d = (k + 1) >> 1;  // k = 0, 1, 2, 3, ... -> n/2, n/2 - 1, n/2 + 1, n/2 - 2, ...: a permutation of 0..n-1
     return (n >> 1) + ((k & 1) ? -d : d);
 }
+// the interleaved order's coordinates of this block (G > 0): group, item within the group, and the
+// tile's position (kx, ky) in the centre-out order.  With L = blockIdx.y gridDim.x + blockIdx.x and
+// G gridDim.x blocks per group, the group is L / (G gridDim.x) = blockIdx.y / G (blockIdx.x <
+// gridDim.x) and r = L mod (G gridDim.x) is the remainder below.
+__device__ __forceinline__ void group_coords(int G, int nx, int& grp, int& item, int& kx, int& ky) {
+    grp = udiv_uniform(blockIdx.y, G);
+    const int r = (blockIdx.y - grp * G) * gridDim.x + blockIdx.x;
+    const int t = udiv_uniform(r, G);
+    item = r - t * G;
+    ky = udiv_uniform(t, nx);
+    kx = t - ky * nx;
+}
 __device__ __forceinline__ void block_item_tile(int G, int nx, int ny, int& b, int& tx, int& ty) {
     if (G > 0) {
-        const int L = blockIdx.y * gridDim.x + blockIdx.x;
-        const int per = G * gridDim.x;  // blocks per group
-        const int grp = L / per, r = L - grp * per;
-        b = grp * G + r % G;
-        const int t = r / G;
-        tx = centre_out(t % nx, nx);
-        ty = centre_out(t / nx, ny);
+        int grp, item, kx, ky;
+        group_coords(G, nx, grp, item, kx, ky);
+        b = grp * G + item;
+        tx = centre_out(kx, nx);
+        ty = centre_out(ky, ny);
         return;
     }
     b = blockIdx.y;

@@ -1,7 +1,8 @@
-# usage: VARIANTS="base lib:abl/libnr_old.so NR_FWD_TIMING A=1,@ENV=2 M:--misched=gcn-max-ilp" bash tools/ablate.sh <tag>
+# usage: VARIANTS="base lib:abl/libnr_old.so NR_FWD_TIMING A=1,@ENV=2 M:--misched=gcn-max-ilp P:tools/ablations/x.patch" bash tools/ablate.sh <tag>
 # builds one library per variant (comma-separated -D defines; "base" = none; a token @VAR=value is an
-# environment setting of that variant's runs instead, M:<opt> an `-mllvm <opt>` code-generation option)
-# and benches each;
+# environment setting of that variant's runs instead, M:<opt> an `-mllvm <opt>` code-generation option,
+# P:<file> a patch (-p1, repository root) applied to a scratch copy of the sources: timing-only
+# variants live in tools/ablations/ as patches, never in the product sources) and benches each;
 # CONFIGS=cfg2,cfg3,cfg5 also times those configs (tools/bench_configs.py); NOHEAD=1 skips the headline.
 set -o pipefail
 # the product's hipcc flags (__graft_entry__.HIPCC_FLAGS without -I); HIPFLAGS overrides them
@@ -18,9 +19,17 @@ for V in $VARIANTS; do
   V0=${V%%,*}
   if [ "${V0#lib:}" != "$V0" ]; then cp "${V0#lib:}" $OUT/lib/libnr_$i.so || exit 1; continue; fi
   DEFS=""
-  if [ "$V" != base ]; then for d in ${V//,/ }; do case $d in @*) ;; base) ;; lib:*) ;; M:*) DEFS="$DEFS -mllvm ${d#M:}";; *) DEFS="$DEFS -D$d";; esac; done; fi
+  PATCHES=""
+  if [ "$V" != base ]; then for d in ${V//,/ }; do case $d in @*) ;; base) ;; lib:*) ;; M:*) DEFS="$DEFS -mllvm ${d#M:}";; P:*) PATCHES="$PATCHES ${d#P:}";; *) DEFS="$DEFS -D$d";; esac; done; fi
+  SRCROOT=.
+  if [ -n "$PATCHES" ]; then
+    SRCROOT=$(mktemp -d)
+    mkdir -p $SRCROOT/neural_renderer_v2_pytorch_amd && cp -r neural_renderer_v2_pytorch_amd/csrc $SRCROOT/neural_renderer_v2_pytorch_amd/ && cp -r include $SRCROOT/ || exit 1
+    for p in $PATCHES; do patch -s -p1 -d $SRCROOT < $p || exit 1; done
+  fi
   /opt/rocm/bin/hipcc $HIPFLAGS \
-  -Iinclude $DEFS neural_renderer_v2_pytorch_amd/csrc/nr_raster.hip -o $OUT/lib/libnr_$i.so || exit 1
+  -I$SRCROOT/include $DEFS $SRCROOT/neural_renderer_v2_pytorch_amd/csrc/nr_raster.hip -o $OUT/lib/libnr_$i.so || exit 1
+  if [ -n "$PATCHES" ]; then rm -rf $SRCROOT; fi
 done
 # REPEAT=n runs the whole variant list n times, interleaved (box-to-box and run-to-run spread is a
 # few per cent); STEPS sets the timed steps per run
