@@ -345,6 +345,50 @@ NR_API int nr_flatten_backward(const float* records, const int32_t* edge_offsets
                                const float* grad_loss, int batch_size, int num_vertices, int num_edges,
                                float* grad_vertices, void* stream);
 
+/* Image losses (image_loss.py): per-item reductions of images [B, N] float32, item b being the N
+ * contiguous floats at images + b * image_stride (strides in elements, >= 0).  targets: item b at
+ * targets + b * target_stride, 0 = one target shared by every item.  No float atomics: losses and
+ * gradients are bitwise reproducible from run to run.
+ *
+ * Pointwise (kind = NR_LOSS_SQUARED or NR_LOSS_HUBER), d_i = x_i - t_i:
+ *   loss_b = sum_i w_i h(d_i),   h(d) = d^2   (squared; no 1/2)
+ *                                h(d) = d^2 / 2 if |d| < delta, else delta (|d| - delta / 2)   (Huber; 0 < delta < inf)
+ *   grad x_i = g_b w_i h'(d_i),  h'(d) = 2 d  (squared);  d if |d| < delta, else delta sign(d)  (Huber)
+ * weights: NULL (w_i = 1), or w_i = weights[b * weight_stride + i % weight_period] with weight_period >= 1
+ * dividing N: N for full weights, H W for a pixel mask shared by the channels; weight_stride 0 = shared.
+ * IoU of silhouettes p against t:
+ *   I_b = sum_i p_i t_i,  U_b = sum_i (p_i + t_i - p_i t_i),  loss_b = 1 - I_b / (U_b + eps)
+ *   grad p_i = -g_b (t_i (U_b + eps) - I_b (1 - t_i)) / (U_b + eps)^2
+ *
+ * Each launch takes 16-byte loads and stores when every item base of images, targets (and grad_images)
+ * is 16-byte aligned, and vector weight loads when the weights' bases are too and weight_period is a
+ * multiple of 4; an N that is no multiple of 4 ends in scalar accesses; any other layout runs scalar.
+ * Limits: N <= INT_MAX - 4096 and B * ceil(N / 4096) <= INT_MAX (NR_ERR_ARGS otherwise).  With B == 0 or
+ * N == 0 no kernel is launched and every output is still fully written (fills on the stream).
+ *
+ * Scratch bytes of a forward: the per-block partial sums [B][ceil(N / 4096)][2]; no zero fill needed. */
+enum { NR_LOSS_SQUARED = 0, NR_LOSS_HUBER = 1 };
+NR_API size_t nr_image_loss_workspace_bytes(int batch_size, int item_elems);
+/* loss [B], fully written (0 when N == 0). */
+NR_API int nr_pointwise_loss_forward(const float* images, long long image_stride, const float* targets,
+                                     long long target_stride, const float* weights, long long weight_stride,
+                                     int weight_period, int kind, float delta, int batch_size, int item_elems,
+                                     float* loss, void* workspace, size_t workspace_bytes, void* stream);
+/* grad_loss [B] -> grad_images [B, N] contiguous, fully written; recomputed from the forward's inputs. */
+NR_API int nr_pointwise_loss_backward(const float* images, long long image_stride, const float* targets,
+                                      long long target_stride, const float* weights, long long weight_stride,
+                                      int weight_period, int kind, float delta, int batch_size, int item_elems,
+                                      const float* grad_loss, float* grad_images, void* stream);
+/* loss [B] and sums [B, 2] = (I_b, U_b), both fully written (N == 0: sums 0, loss 1 - 0 / (0 + eps)). */
+NR_API int nr_iou_loss_forward(const float* images, long long image_stride, const float* targets,
+                               long long target_stride, float eps, int batch_size, int item_elems, float* loss,
+                               float* sums, void* workspace, size_t workspace_bytes, void* stream);
+/* grad_loss [B] -> grad_images [B, N] contiguous, fully written, from the forward's sums and the targets
+ * (the gradient does not depend on p_i, so the silhouettes are not an argument). */
+NR_API int nr_iou_loss_backward(const float* targets, long long target_stride, const float* sums, float eps,
+                                int batch_size, int item_elems, const float* grad_loss, float* grad_images,
+                                void* stream);
+
 /* Diagnostics (no reference counterpart): the kernels replace some IEEE divisions by a shortened
  * form of the compiler's own division sequence inside a guarded operand range (DESIGN.md,
  * "Numerics").  This runs both forms on n operand pairs so tests can check they agree bit for bit. */

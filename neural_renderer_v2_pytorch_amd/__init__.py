@@ -19,5 +19,7 @@ from .differentiation import differentiation
 from .camera import camera_transform, projection_transform
 from .mesh_loss import (FlattenLoss, LaplacianLoss, MeshTopology, flatten_loss, flatten_loss_torch, laplacian_loss,
                         laplacian_loss_torch, mesh_topology)
+from .image_loss import (HuberLoss, IoULoss, SquaredErrorLoss, huber_loss, huber_loss_torch, iou_loss, iou_loss_torch,
+                         squared_error_loss, squared_error_loss_torch)
 
 __version__ = '2.0.2+mi355x.1'

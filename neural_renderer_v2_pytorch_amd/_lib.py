@@ -29,6 +29,8 @@ EXPORTS = [
     "nr_projection_args_size", "nr_projection_forward", "nr_projection_workspace_bytes", "nr_projection_backward",
     "nr_mesh_loss_workspace_bytes", "nr_laplacian_forward", "nr_laplacian_backward", "nr_flatten_forward",
     "nr_flatten_backward",
+    "nr_image_loss_workspace_bytes", "nr_pointwise_loss_forward", "nr_pointwise_loss_backward", "nr_iou_loss_forward",
+    "nr_iou_loss_backward",
 ]
 
 ABI_VERSION = 6  # include/nr_raster.h NR_ABI_VERSION
@@ -64,6 +66,7 @@ class NrRasterArgs(ctypes.Structure):
 
 NR_LIGHT_AMBIENT, NR_LIGHT_DIRECTIONAL, NR_LIGHT_SPECULAR, NR_LIGHT_FLOATS = 0, 1, 2, 8
 NR_CAMERA_NONE, NR_CAMERA_LOOK_AT, NR_CAMERA_LOOK = 0, 1, 2
+NR_LOSS_SQUARED, NR_LOSS_HUBER = 0, 1
 
 
 class NrCameraArgs(ctypes.Structure):  # include/nr_raster.h
@@ -94,7 +97,7 @@ def lib():
         raise RuntimeError("neural_renderer_v2_pytorch_amd: HIP library %s is missing; build it with "
                            "__graft_entry__.build() (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    # additions within one ABI version (the nr_projection_* and mesh-loss entry points): a library built before them
+    # additions within one ABI version (the nr_projection_*, mesh-loss and image-loss entry points): a library built before them
     # still reports the version this binding expects
     missing = [name for name in EXPORTS if not hasattr(L, name)]
     if missing:
@@ -139,6 +142,14 @@ def lib():
     L.nr_flatten_forward.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
                                      c_void_p]
     L.nr_flatten_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
+    L.nr_image_loss_workspace_bytes.restype = c_size_t
+    L.nr_image_loss_workspace_bytes.argtypes = [c_int, c_int]
+    pointwise = [c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, c_float, c_int, c_int]
+    L.nr_pointwise_loss_forward.argtypes = pointwise + [c_void_p, c_void_p, c_size_t, c_void_p]
+    L.nr_pointwise_loss_backward.argtypes = pointwise + [c_void_p, c_void_p, c_void_p]
+    L.nr_iou_loss_forward.argtypes = [c_void_p, c_ll, c_void_p, c_ll, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_size_t, c_void_p]
+    L.nr_iou_loss_backward.argtypes = [c_void_p, c_ll, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p]
     L.nr_backward_workspace_bytes.restype = c_size_t
     L.nr_backward_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int]
     L.nr_raster_args_size.restype = c_size_t
@@ -155,7 +166,8 @@ def lib():
         if name not in ("nr_last_error", "nr_workspace_bytes", "nr_num_channels", "nr_backward_workspace_bytes",
                         "nr_halo_bytes", "nr_raster_args_size", "nr_camera_workspace_bytes",
                         "nr_texture_packed_bytes", "nr_hot_acc_bytes", "nr_projection_args_size",
-                        "nr_projection_workspace_bytes", "nr_mesh_loss_workspace_bytes"):
+                        "nr_projection_workspace_bytes", "nr_mesh_loss_workspace_bytes",
+                        "nr_image_loss_workspace_bytes"):
             getattr(L, name).restype = c_int
     # a library of another ABI revision (an NR_LIB_PATH override, a stale build) would misread the
     # arguments (e.g. an older nr_rasterize_backward takes its stream where workspace_zeroed is now)

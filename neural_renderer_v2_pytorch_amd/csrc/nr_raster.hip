@@ -25,7 +25,8 @@
 // per-pixel shading, XCD tile map), nr_fwd.h (setup + face-index raster), nr_shade.h (image epilogue,
 // halo cache, standalone reference kernels), nr_bwd.h (backward), nr_camera.h (look_at / look +
 // perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian and
-// flatten regularizers), nr_host.h (argument checks); this file holds the extern "C" ABI.
+// flatten regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_host.h (argument
+// checks); this file holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -53,6 +54,7 @@
 #include "nr_camera.h"
 #include "nr_projection.h"
 #include "nr_mesh_loss.h"
+#include "nr_image_loss.h"
 #include "nr_host.h"
 
 
@@ -888,6 +890,136 @@ int nr_flatten_backward(const float* records, const int32_t* edge_offsets, const
     nr_launch(k_flat_bwd_gather, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, (hipStream_t)stream, records, edge_offsets,
               edge_slots, grad_loss, V, E2, nblk, grad_vertices);
     return check_launch("k_flat_bwd_gather");
+}
+
+// ---- image losses (nr_image_loss.h) ----
+static long long il_chunks(int n) { return ((long long)n + IL_CHUNK - 1) / IL_CHUNK; }
+
+static int validate_image_loss(int B, int N) {
+    if (B < 0 || N < 0) return fail(NR_ERR_ARGS, "bad sizes B=%d N=%d", B, N);
+    if (N > INT_MAX - IL_CHUNK || (long long)B * il_chunks(N) > INT_MAX) return fail(NR_ERR_ARGS, "too many elements B=%d N=%d", B, N);
+    return NR_OK;
+}
+
+// every item base p + b * stride, b < B, on 16 bytes
+static bool il_aligned(const void* p, long long stride, int B) { return ((uintptr_t)p & 15) == 0 && (B == 1 || (stride & 3) == 0); }
+
+size_t nr_image_loss_workspace_bytes(int batch_size, int item_elems) {
+    if (batch_size <= 0 || item_elems <= 0) return 0;
+    return align_up((size_t)batch_size * (size_t)il_chunks(item_elems) * 2 * 4);
+}
+
+// The checked kernel arguments of both pointwise entry points, and the instantiation: vec (VW = 4) and wm.
+static int pointwise_args(const float* images, long long istride, const float* targets, long long tstride, const float* weights,
+                          long long wstride, int period, int kind, float delta, int B, int N, const float* grad_images,
+                          ILPointwise* a, bool* vec, int* wm) {
+    if (!images || !targets) return fail(NR_ERR_ARGS, "null images or targets");
+    if (istride < 0 || tstride < 0 || wstride < 0) return fail(NR_ERR_ARGS, "negative item stride");
+    if (kind != NR_LOSS_SQUARED && kind != NR_LOSS_HUBER) return fail(NR_ERR_ARGS, "bad kind %d", kind);
+    if (kind == NR_LOSS_HUBER && !(delta > 0.f && delta < INFINITY)) return fail(NR_ERR_ARGS, "bad delta %g", (double)delta);
+    if (weights && (period <= 0 || N % period != 0)) return fail(NR_ERR_ARGS, "the weight period %d must divide N=%d", period, N);
+    *vec = il_aligned(images, istride, B) && il_aligned(targets, tstride, B) && (!grad_images || il_aligned(grad_images, N, B));
+    *wm = !weights ? IL_W_NONE : (*vec && il_aligned(weights, wstride, B) && period % 4 == 0) ? IL_W_VECTOR : IL_W_SCALAR;
+    *a = ILPointwise{images, targets, weights, istride, tstride, wstride, weights ? period : 1,
+                     weights ? (IL_BLOCK * 4) % period : 0, delta, N, (int)il_chunks(N)};
+    return NR_OK;
+}
+
+int nr_pointwise_loss_forward(const float* images, long long image_stride, const float* targets, long long target_stride,
+                              const float* weights, long long weight_stride, int weight_period, int kind, float delta,
+                              int batch_size, int item_elems, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+    const int B = batch_size, N = item_elems;
+    int e = validate_image_loss(B, N);
+    if (e) return e;
+    if (B == 0) return NR_OK;
+    if (!loss) return fail(NR_ERR_ARGS, "null loss");
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) {
+        if (hipMemsetAsync(loss, 0, (size_t)B * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");
+        return NR_OK;
+    }
+    ILPointwise a;
+    bool vec;
+    int wm;
+    e = pointwise_args(images, image_stride, targets, target_stride, weights, weight_stride, weight_period, kind, delta, B, N,
+                       nullptr, &a, &vec, &wm);
+    if (e) return e;
+    if (!workspace || workspace_bytes < nr_image_loss_workspace_bytes(B, N))
+        return fail(NR_ERR_WORKSPACE, "image loss workspace missing or too small");
+    launch_pointwise(a, vec, wm, kind == NR_LOSS_HUBER, B, st, nullptr, (float*)workspace);
+    e = check_launch("k_pointwise_fwd");
+    if (e) return e;
+    nr_launch(k_mesh_loss_sum, dim3((unsigned)B), dim3(ML_BLOCK), 0, st, (const float*)workspace, a.nchunk, loss);
+    return check_launch("k_mesh_loss_sum");
+}
+
+int nr_pointwise_loss_backward(const float* images, long long image_stride, const float* targets, long long target_stride,
+                               const float* weights, long long weight_stride, int weight_period, int kind, float delta,
+                               int batch_size, int item_elems, const float* grad_loss, float* grad_images, void* stream) {
+    const int B = batch_size, N = item_elems;
+    int e = validate_image_loss(B, N);
+    if (e) return e;
+    if (B == 0 || N == 0) return NR_OK;
+    if (!grad_loss || !grad_images) return fail(NR_ERR_ARGS, "null grad_loss or grad_images");
+    ILPointwise a;
+    bool vec;
+    int wm;
+    e = pointwise_args(images, image_stride, targets, target_stride, weights, weight_stride, weight_period, kind, delta, B, N,
+                       grad_images, &a, &vec, &wm);
+    if (e) return e;
+    launch_pointwise(a, vec, wm, kind == NR_LOSS_HUBER, B, (hipStream_t)stream, grad_loss, grad_images);
+    return check_launch("k_pointwise_bwd");
+}
+
+int nr_iou_loss_forward(const float* images, long long image_stride, const float* targets, long long target_stride, float eps,
+                        int batch_size, int item_elems, float* loss, float* sums, void* workspace, size_t workspace_bytes,
+                        void* stream) {
+    const int B = batch_size, N = item_elems;
+    int e = validate_image_loss(B, N);
+    if (e) return e;
+    if (B == 0) return NR_OK;
+    if (!loss || !sums) return fail(NR_ERR_ARGS, "null loss or sums");
+    hipStream_t st = (hipStream_t)stream;
+    if (N == 0) {
+        const float one = 1.f - 0.f / (0.f + eps);  // 1, or NaN with eps == 0 as the formula has it
+        int bits;
+        memcpy(&bits, &one, 4);
+        if (hipMemsetAsync(sums, 0, (size_t)B * 8, st) != hipSuccess || hipMemsetD32Async((hipDeviceptr_t)loss, bits, (size_t)B, st) != hipSuccess)
+            return check_launch("hipMemsetAsync");
+        return NR_OK;
+    }
+    if (!images || !targets) return fail(NR_ERR_ARGS, "null images or targets");
+    if (image_stride < 0 || target_stride < 0) return fail(NR_ERR_ARGS, "negative item stride");
+    if (!workspace || workspace_bytes < nr_image_loss_workspace_bytes(B, N))
+        return fail(NR_ERR_WORKSPACE, "image loss workspace missing or too small");
+    const int nchunk = (int)il_chunks(N);
+    const dim3 grid((unsigned)(B * nchunk));
+    if (il_aligned(images, image_stride, B) && il_aligned(targets, target_stride, B))
+        nr_launch(k_iou_fwd<4>, grid, dim3(IL_BLOCK), 0, st, images, image_stride, targets, target_stride, N, nchunk, (float*)workspace);
+    else
+        nr_launch(k_iou_fwd<1>, grid, dim3(IL_BLOCK), 0, st, images, image_stride, targets, target_stride, N, nchunk, (float*)workspace);
+    e = check_launch("k_iou_fwd");
+    if (e) return e;
+    nr_launch(k_iou_finish, dim3((unsigned)B), dim3(IL_BLOCK), 0, st, (const float*)workspace, nchunk, eps, sums, loss);
+    return check_launch("k_iou_finish");
+}
+
+int nr_iou_loss_backward(const float* targets, long long target_stride, const float* sums, float eps, int batch_size,
+                         int item_elems, const float* grad_loss, float* grad_images, void* stream) {
+    const int B = batch_size, N = item_elems;
+    int e = validate_image_loss(B, N);
+    if (e) return e;
+    if (B == 0 || N == 0) return NR_OK;
+    if (!targets || !sums || !grad_loss || !grad_images) return fail(NR_ERR_ARGS, "null pointer");
+    if (target_stride < 0) return fail(NR_ERR_ARGS, "negative item stride");
+    const int nchunk = (int)il_chunks(N);
+    const dim3 grid((unsigned)(B * nchunk));
+    hipStream_t st = (hipStream_t)stream;
+    if (il_aligned(targets, target_stride, B) && il_aligned(grad_images, N, B))
+        nr_launch(k_iou_bwd<4>, grid, dim3(IL_BLOCK), 0, st, targets, target_stride, sums, grad_loss, eps, N, nchunk, grad_images);
+    else
+        nr_launch(k_iou_bwd<1>, grid, dim3(IL_BLOCK), 0, st, targets, target_stride, sums, grad_loss, eps, N, nchunk, grad_images);
+    return check_launch("k_iou_bwd");
 }
 
 int nr_selftest_division(const float* a, const float* b, float* q_fast, float* q_ieee, long long n, void* stream) {
