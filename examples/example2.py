@@ -5,7 +5,10 @@ vertices are an nn.Parameter, the loss is the squared difference between the ren
 and the reference image (viewed from azimuth 90), and Adam steps the vertices.  Every render and
 its backward run through the HIP rasterizer (Renderer.render_silhouettes -> rasterize_core).
 
-    python examples/example2.py [--iters 300] [--frames DIR] [--gif out.gif]
+    python examples/example2.py [--iters 300] [--frames DIR] [--gif out.gif] [--optimizer torch|fused]
+
+--optimizer fused steps the vertices with the package's own Adam (nr.Adam: one fused HIP launch pair, the
+same rule up to rounding) in place of torch.optim.Adam.
 
 Inputs default to tests/data/teapot.obj and tests/data/example2_ref.png (the reference example's
 own data files).
@@ -44,9 +47,18 @@ class SilhouetteFit(torch.nn.Module):
         return torch.sum((self.render() - self.image_ref[None]) ** 2)
 
 
-def optimize(model, iters, frames_dir=None):
+def make_optimizer(model, optimizer, capturable=False):
+    """'torch': torch.optim.Adam (capturable for a graphed step); 'fused': nr.Adam, which needs no flag."""
+    if optimizer == 'fused':
+        return nr.Adam(model.parameters())
+    if optimizer != 'torch':
+        raise ValueError("optimizer must be 'torch' or 'fused', got %r" % (optimizer,))
+    return torch.optim.Adam(model.parameters(), capturable=True) if capturable else torch.optim.Adam(model.parameters())
+
+
+def optimize(model, iters, frames_dir=None, optimizer='torch'):
     """example2.py:62-80: Adam over the vertices; returns the loss of every step."""
-    opt = torch.optim.Adam(model.parameters())
+    opt = make_optimizer(model, optimizer)
     losses = []
     for i in range(iters):
         opt.zero_grad()
@@ -59,15 +71,15 @@ def optimize(model, iters, frames_dir=None):
     return losses
 
 
-def optimize_graphed(model, iters):
+def optimize_graphed(model, iters, optimizer='torch'):
     """optimize() with the whole step -- camera, rasterize, loss, backward, Adam -- captured once in a
     HIP graph (torch.cuda.CUDAGraph) and replayed: the same kernels without the per-launch host
-    cost.  The viewpoint is held as a device tensor and Adam runs with capturable=True, so nothing
+    cost.  The viewpoint is held as a device tensor and Adam runs with capturable=True (nr.Adam: as it is), so nothing
     in the step touches the host; returns the loss of every step."""
     dev = model.vertices.device
     model.renderer.viewpoints = torch.as_tensor(
         nr.get_points_from_angles(CAMERA_DISTANCE, ELEVATION, AZIMUTH), dtype=torch.float32, device=dev)
-    opt = torch.optim.Adam(model.parameters(), capturable=True)
+    opt = make_optimizer(model, optimizer, capturable=True)
 
     def step():
         loss = torch.sum((model.renderer.render_silhouettes(model.vertices, model.faces) - model.image_ref[None]) ** 2)
@@ -118,11 +130,15 @@ def main():
     ap.add_argument('--frames', default=None, help='directory for per-step frames (and the GIFs)')
     ap.add_argument('--gpu', type=int, default=0)
     ap.add_argument('--graph', action='store_true', help='replay the step as a HIP graph (no frames)')
+    ap.add_argument('--optimizer', choices=('torch', 'fused'), default='torch', help='torch.optim.Adam or nr.Adam')
     args = ap.parse_args()
     model = SilhouetteFit(args.obj, args.ref, torch.device('cuda', args.gpu))
     if args.frames:
         os.makedirs(args.frames, exist_ok=True)
-    losses = optimize_graphed(model, args.iters) if args.graph else optimize(model, args.iters, args.frames)
+    if args.graph:
+        losses = optimize_graphed(model, args.iters, args.optimizer)
+    else:
+        losses = optimize(model, args.iters, args.frames, args.optimizer)
     print('loss: first %.1f, last %.1f after %d steps' % (losses[0], losses[-1], len(losses)))
     if args.frames:
         make_gif(args.frames, os.path.join(args.frames, 'example2_opt.gif'))

@@ -389,6 +389,61 @@ NR_API int nr_iou_loss_backward(const float* targets, long long target_stride, c
                                 int batch_size, int item_elems, const float* grad_loss, float* grad_images,
                                 void* stream);
 
+/* Optimiser (optimizers.py): Adam over a list of float32 tensors, with the two rules of the reference's
+ * optimizers.py:1-37: an element whose gradient is zero is left alone (skip_zero_grad), and each tensor
+ * scales the rate by its own lr_scale (the reference's param.lr).  One call advances every listed
+ * tensor's step and updates it, NR_ADAM_MAX_TENSORS tensors per launch pair (k_adam_tick, k_adam_update).
+ *
+ * Per tensor, with t = its step after the increment (step: one float32 on the device, as
+ * torch.optim.Adam(capturable=True) keeps it):
+ *   c1 = (float)(1 - beta1)      c2 = (float)(1 - beta2)             (from the double arguments)
+ *   step_size = (float)(lr * lr_scale / (1 - beta1^t))               (computed in double)
+ *   inv_sqrt_bc2 = (float)(1 / sqrt(1 - beta2^t))                    (computed in double)
+ * and per element, in float32, in this order, with no contraction:
+ *   if skip_zero_grad and g == 0: leave p, m, v as they are          (both zeros count; NaN does not)
+ *   m = m + c1 * (g - m)
+ *   v = v + c2 * (g * g - v);   v = v < 0 ? 0 : v                    (the reference's clamp, optimizers.py:25)
+ *   p = p - step_size * (m / (sqrt(v) * inv_sqrt_bc2 + eps))
+ * Without skip_zero_grad and with lr_scale = 1 this is torch.optim.Adam's rule (amsgrad = False, no weight
+ * decay, maximize = False) up to rounding.  With skip_zero_grad the step still advances per tensor and a
+ * skipped element's moments do not decay (lazy Adam).
+ *
+ * lr: the host double, or, with lr_device non-null, the float32 read from the device by the tick kernel (a
+ * schedule can change it between replays of a captured step); lr must be finite either way.  The factor
+ * scratch holds (step_size, inv_sqrt_bc2) per listed tensor, in list order, written by the tick kernel of
+ * this call: it belongs to the caller, needs no fill, and must not be shared by calls that may overlap.
+ * A tensor takes 16-byte accesses when param, grad, exp_avg and exp_avg_sq are all 16-byte aligned and
+ * lane-consecutive scalar accesses otherwise, with bitwise identical results.  The listed tensors must not
+ * overlap each other, and no two may share a step.  A tensor with numel == 0 takes no blocks (its step,
+ * when given, still advances).
+ * Checked before any launch (NR_ERR_ARGS): 0 <= num_tensors <= tensors_capacity (the length of the host
+ * array), non-null param / grad / exp_avg / exp_avg_sq / step for every tensor with numel > 0,
+ * 0 <= numel <= INT_MAX - NR_ADAM_CHUNK, finite lr and lr_scale, 0 <= beta1, beta2 < 1, eps >= 0; a missing
+ * or short scratch is NR_ERR_WORKSPACE.  Never synchronises with the host. */
+enum { NR_ADAM_MAX_TENSORS = 24, NR_ADAM_CHUNK = 4096 /* elements of one tensor per block */ };
+typedef struct NrAdamTensor {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    float* step;
+    long long numel;
+    double lr_scale;
+} NrAdamTensor;
+typedef struct NrAdamArgs {
+    int num_tensors;
+    int tensors_capacity;
+    const NrAdamTensor* tensors; /* host array */
+    double lr, beta1, beta2, eps;
+    const float* lr_device;
+    int skip_zero_grad;
+    void* scratch;
+    size_t scratch_bytes;
+} NrAdamArgs;
+NR_API size_t nr_adam_args_size(void);
+NR_API size_t nr_adam_scratch_bytes(int num_tensors);
+NR_API int nr_adam_step(const NrAdamArgs* args, void* stream);
+
 /* Diagnostics (no reference counterpart): the kernels replace some IEEE divisions by a shortened
  * form of the compiler's own division sequence inside a guarded operand range (DESIGN.md,
  * "Numerics").  This runs both forms on n operand pairs so tests can check they agree bit for bit. */

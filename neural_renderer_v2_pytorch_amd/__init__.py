@@ -1,7 +1,7 @@
 """neural_renderer_v2_pytorch_amd -- MI355X-native drop-in for neural_renderer_torch's rasterize path.
 
-Public surface mirrors the reference's neural_renderer_torch/__init__.py:1-14 (minus Mesh and the
-chainer-based Adam, which are outside the hot path).  Compute runs in hand-written HIP kernels for
+Public surface mirrors the reference's neural_renderer_torch/__init__.py:1-14 (minus Mesh; the
+reference's chainer-based Adam is optimizers.Adam here).  Compute runs in hand-written HIP kernels for
 gfx950 (csrc/nr_raster.hip) behind the C ABI of include/nr_raster.h; there is no CPU fallback.
 """
 from .lights import AmbientLight, DirectionalLight, Light, SpecularLight
@@ -21,5 +21,6 @@ from .mesh_loss import (FlattenLoss, LaplacianLoss, MeshTopology, flatten_loss, 
                         laplacian_loss_torch, mesh_topology)
 from .image_loss import (HuberLoss, IoULoss, SquaredErrorLoss, huber_loss, huber_loss_torch, iou_loss, iou_loss_torch,
                          squared_error_loss, squared_error_loss_torch)
+from .optimizers import Adam, adam_step_torch
 
 __version__ = '2.0.2+mi355x.1'

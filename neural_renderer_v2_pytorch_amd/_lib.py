@@ -31,6 +31,7 @@ EXPORTS = [
     "nr_flatten_backward",
     "nr_image_loss_workspace_bytes", "nr_pointwise_loss_forward", "nr_pointwise_loss_backward", "nr_iou_loss_forward",
     "nr_iou_loss_backward",
+    "nr_adam_args_size", "nr_adam_scratch_bytes", "nr_adam_step",
 ]
 
 ABI_VERSION = 6  # include/nr_raster.h NR_ABI_VERSION
@@ -67,6 +68,7 @@ class NrRasterArgs(ctypes.Structure):
 NR_LIGHT_AMBIENT, NR_LIGHT_DIRECTIONAL, NR_LIGHT_SPECULAR, NR_LIGHT_FLOATS = 0, 1, 2, 8
 NR_CAMERA_NONE, NR_CAMERA_LOOK_AT, NR_CAMERA_LOOK = 0, 1, 2
 NR_LOSS_SQUARED, NR_LOSS_HUBER = 0, 1
+NR_ADAM_MAX_TENSORS, NR_ADAM_CHUNK = 24, 4096  # tensors per launch pair, elements of one tensor per block
 
 
 class NrCameraArgs(ctypes.Structure):  # include/nr_raster.h
@@ -86,6 +88,21 @@ class NrProjectionArgs(ctypes.Structure):  # include/nr_raster.h
     ]
 
 
+class NrAdamTensor(ctypes.Structure):  # include/nr_raster.h
+    _fields_ = [
+        ("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p), ("step", c_void_p),
+        ("numel", c_ll), ("lr_scale", ctypes.c_double),
+    ]
+
+
+class NrAdamArgs(ctypes.Structure):  # include/nr_raster.h
+    _fields_ = [
+        ("num_tensors", c_int), ("tensors_capacity", c_int), ("tensors", ctypes.POINTER(NrAdamTensor)),
+        ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+        ("lr_device", c_void_p), ("skip_zero_grad", c_int), ("scratch", c_void_p), ("scratch_bytes", c_size_t),
+    ]
+
+
 _lib = None
 
 
@@ -97,7 +114,7 @@ def lib():
         raise RuntimeError("neural_renderer_v2_pytorch_amd: HIP library %s is missing; build it with "
                            "__graft_entry__.build() (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    # additions within one ABI version (the nr_projection_*, mesh-loss and image-loss entry points): a library built before them
+    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss and nr_adam_* entry points): a library built before them
     # still reports the version this binding expects
     missing = [name for name in EXPORTS if not hasattr(L, name)]
     if missing:
@@ -150,6 +167,11 @@ def lib():
     L.nr_iou_loss_forward.argtypes = [c_void_p, c_ll, c_void_p, c_ll, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                       c_size_t, c_void_p]
     L.nr_iou_loss_backward.argtypes = [c_void_p, c_ll, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.nr_adam_args_size.restype = c_size_t
+    L.nr_adam_args_size.argtypes = []
+    L.nr_adam_scratch_bytes.restype = c_size_t
+    L.nr_adam_scratch_bytes.argtypes = [c_int]
+    L.nr_adam_step.argtypes = [ctypes.POINTER(NrAdamArgs), c_void_p]
     L.nr_backward_workspace_bytes.restype = c_size_t
     L.nr_backward_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int]
     L.nr_raster_args_size.restype = c_size_t
@@ -167,7 +189,7 @@ def lib():
                         "nr_halo_bytes", "nr_raster_args_size", "nr_camera_workspace_bytes",
                         "nr_texture_packed_bytes", "nr_hot_acc_bytes", "nr_projection_args_size",
                         "nr_projection_workspace_bytes", "nr_mesh_loss_workspace_bytes",
-                        "nr_image_loss_workspace_bytes"):
+                        "nr_image_loss_workspace_bytes", "nr_adam_args_size", "nr_adam_scratch_bytes"):
             getattr(L, name).restype = c_int
     # a library of another ABI revision (an NR_LIB_PATH override, a stale build) would misread the
     # arguments (e.g. an older nr_rasterize_backward takes its stream where workspace_zeroed is now)
@@ -175,6 +197,10 @@ def lib():
         raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has a %d-byte NrProjectionArgs; this binding needs %d "
                            "bytes (rebuild with __graft_entry__.build())"
                            % (LIB_PATH, L.nr_projection_args_size(), ctypes.sizeof(NrProjectionArgs)))
+    if L.nr_adam_args_size() != ctypes.sizeof(NrAdamArgs):
+        raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has a %d-byte NrAdamArgs; this binding needs %d bytes "
+                           "(rebuild with __graft_entry__.build())"
+                           % (LIB_PATH, L.nr_adam_args_size(), ctypes.sizeof(NrAdamArgs)))
     if L.nr_version() != ABI_VERSION or L.nr_raster_args_size() != ctypes.sizeof(NrRasterArgs):
         raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has ABI version %d with a %d-byte NrRasterArgs; this "
                            "binding needs version %d and %d bytes (rebuild with __graft_entry__.build())"

@@ -25,8 +25,8 @@
 // per-pixel shading, XCD tile map), nr_fwd.h (setup + face-index raster), nr_shade.h (image epilogue,
 // halo cache, standalone reference kernels), nr_bwd.h (backward), nr_camera.h (look_at / look +
 // perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian and
-// flatten regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_host.h (argument
-// checks); this file holds the extern "C" ABI.
+// flatten regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_adam.h
+// (multi-tensor Adam), nr_host.h (argument checks); this file holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -55,6 +55,7 @@
 #include "nr_projection.h"
 #include "nr_mesh_loss.h"
 #include "nr_image_loss.h"
+#include "nr_adam.h"
 #include "nr_host.h"
 
 
@@ -1020,6 +1021,73 @@ int nr_iou_loss_backward(const float* targets, long long target_stride, const fl
     else
         nr_launch(k_iou_bwd<1>, grid, dim3(IL_BLOCK), 0, st, targets, target_stride, sums, grad_loss, eps, N, nchunk, grad_images);
     return check_launch("k_iou_bwd");
+}
+
+// ---- optimiser (nr_adam.h) ----
+size_t nr_adam_args_size(void) { return sizeof(NrAdamArgs); }
+
+size_t nr_adam_scratch_bytes(int num_tensors) {
+    if (num_tensors <= 0) return 0;
+    return align_up((size_t)num_tensors * 2 * 4);
+}
+
+int nr_adam_step(const NrAdamArgs* args, void* stream) {
+    if (!args) return fail(NR_ERR_ARGS, "null adam args");
+    const int n = args->num_tensors;
+    if (n < 0 || n > args->tensors_capacity) return fail(NR_ERR_ARGS, "bad tensor count %d (the array holds %d)", n, args->tensors_capacity);
+    if (n == 0) return NR_OK;
+    if (!args->tensors) return fail(NR_ERR_ARGS, "null tensor array");
+    if (!(args->beta1 >= 0.0 && args->beta1 < 1.0) || !(args->beta2 >= 0.0 && args->beta2 < 1.0))
+        return fail(NR_ERR_ARGS, "bad betas (%g, %g): need 0 <= beta < 1", args->beta1, args->beta2);
+    if (!(args->eps >= 0.0) || !(args->eps < INFINITY)) return fail(NR_ERR_ARGS, "bad eps %g", args->eps);
+    if (!isfinite(args->lr)) return fail(NR_ERR_ARGS, "bad lr %g", args->lr);
+    for (int i = 0; i < n; i++) {
+        const NrAdamTensor& t = args->tensors[i];
+        if (t.numel < 0 || t.numel > (long long)INT_MAX - AD_CHUNK) return fail(NR_ERR_ARGS, "tensor %d: bad numel %lld", i, t.numel);
+        if (t.numel > 0 && (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || !t.step))
+            return fail(NR_ERR_ARGS, "tensor %d: null param, grad, exp_avg, exp_avg_sq or step", i);
+        if (!isfinite(t.lr_scale)) return fail(NR_ERR_ARGS, "tensor %d: bad lr_scale %g", i, t.lr_scale);
+    }
+    if (!args->scratch || args->scratch_bytes < nr_adam_scratch_bytes(n))
+        return fail(NR_ERR_WORKSPACE, "adam factor scratch missing or too small");
+    hipStream_t st = (hipStream_t)stream;
+    for (int base = 0; base < n; base += NR_ADAM_MAX_TENSORS) {
+        const int cnt = min(n - base, (int)NR_ADAM_MAX_TENSORS);
+        AdamTick tick = {};
+        AdamLaunch up = {};
+        long long blocks = 0;
+        for (int i = 0; i < cnt; i++) {
+            const NrAdamTensor& t = args->tensors[base + i];
+            if (t.step) {
+                tick.step[tick.n] = t.step, tick.lr_scale[tick.n] = t.lr_scale, tick.slot[tick.n] = base + i;
+                tick.n++;
+            }
+            if (t.numel == 0) continue;
+            const bool vec = (((uintptr_t)t.param | (uintptr_t)t.grad | (uintptr_t)t.exp_avg | (uintptr_t)t.exp_avg_sq) & 15) == 0;
+            up.t[up.n] = AdamDesc{t.param, t.grad, t.exp_avg, t.exp_avg_sq, (int)t.numel, vec ? 1 : 0, base + i, 0};
+            up.start[up.n] = (int)blocks;
+            blocks += (t.numel + AD_CHUNK - 1) / AD_CHUNK;
+            up.n++;
+        }
+        if (blocks > INT_MAX) return fail(NR_ERR_ARGS, "too many elements in one launch (%lld blocks)", blocks);
+        for (int i = up.n; i <= NR_ADAM_MAX_TENSORS; i++) up.start[i] = (int)blocks;
+        if (tick.n > 0) {
+            tick.lr = args->lr, tick.beta1 = args->beta1, tick.beta2 = args->beta2;
+            tick.lr_device = args->lr_device, tick.factors = (float*)args->scratch;
+            nr_launch(k_adam_tick, dim3(1), dim3(64), 0, st, tick);
+            int e = check_launch("k_adam_tick");
+            if (e) return e;
+        }
+        if (blocks > 0) {
+            up.c1 = (float)(1.0 - args->beta1), up.c2 = (float)(1.0 - args->beta2), up.eps = (float)args->eps;
+            up.factors = (const float*)args->scratch;
+            if (args->skip_zero_grad) nr_launch(k_adam_update<true>, dim3((unsigned)blocks), dim3(AD_BLOCK), 0, st, up);
+            else nr_launch(k_adam_update<false>, dim3((unsigned)blocks), dim3(AD_BLOCK), 0, st, up);
+            int e = check_launch("k_adam_update");
+            if (e) return e;
+        }
+    }
+    return NR_OK;
 }
 
 int nr_selftest_division(const float* a, const float* b, float* q_fast, float* q_ieee, long long n, void* stream) {
