@@ -444,6 +444,64 @@ NR_API size_t nr_adam_args_size(void);
 NR_API size_t nr_adam_scratch_bytes(int num_tensors);
 NR_API int nr_adam_step(const NrAdamArgs* args, void* stream);
 
+/* Vertex attributes (attributes.py): any per-vertex table [Va, C] rendered as an image [B, C, s, s], in
+ * place of rgb_map in rasterize_core (rasterize.py:227-329).  The caller first runs nr_rasterize_forward
+ * with NR_DRAW_SILHOUETTES alone, face_index_sparse = 0 and no halo, and hands its face_index [B, S, S]
+ * and face_records [B, F, 16] over (S = 2 s with anti-aliasing, else s).  Per foreground pixel of face f
+ * with the weights w_k of compute_weight_map, corner depths z_k and corner rows a_k = attributes[b,
+ * faces_attributes[f, k]]:
+ *   linear:               out_c = sum_k w_k a_kc                                    (rasterize.py:185-187)
+ *   perspective-correct:  q_k = w_k / (z_k + 1e-10),  Dn = sum_k (q_k + 1e-10),
+ *                         out_c = (sum_k q_k a_kc) / Dn                             (rasterize.py:113-119)
+ * no clamp; background pixels 0.  The image is the internal one [B, S, S, C] permuted to [B, C, S, S],
+ * flipped along both image axes and, with anti-aliasing, averaged over 2x2 (rasterize.py:315-328).
+ * Backward, for the internal-pixel upstream g_c and the soft gradient (gx, gy) of Differentiation.backward
+ * (differentiation.py:12-36) on the internal image:
+ *   d a_kc: w_k g_c (linear), (q_k / Dn) g_c (perspective-correct)
+ *   d vertex (x, y): w_k (gx, gy);   d vertex z: -(q_k / (z_k + 1e-10)) / Dn sum_c g_c (a_kc - out_c)
+ *   (perspective-correct; 0 in the linear mode), added at vertex faces[f, k] and row faces_attributes[f, k].
+ * The sums over a wave's pixels use float atomics into per-face-corner records: gradients agree from run
+ * to run up to the order of float additions; the sums over the records keep a fixed order.
+ * Limits: 1 <= C <= NR_ATTR_MAX_CHANNELS, S <= 16384, B <= 65535 (NR_ERR_ARGS otherwise).  The index arrays
+ * are trusted: face_index below F, faces_attributes below Va, CSR entries below 3 F.  With B, F or V equal
+ * to 0 no kernel is launched and every output is still fully written (fills on the stream). */
+enum { NR_ATTR_MAX_CHANNELS = 64 };
+typedef struct NrAttributeArgs {
+    int batch_size;               /* B */
+    int num_faces;                /* F */
+    int num_vertices;             /* V */
+    int num_attributes;           /* Va: rows of the attribute table */
+    int num_channels;             /* C */
+    int image_size;               /* s */
+    int anti_aliasing;            /* internal S = 2 s when set */
+    int perspective_correct;
+    const int32_t* face_index;    /* [B, S, S], fully written by the forward (-1 = background) */
+    const float* face_records;    /* [B, F, 16] */
+    const int32_t* faces;         /* [F, 3] vertex indices (the layout the vertex CSR was built from; not read) */
+    const int32_t* faces_attributes; /* [F, 3] attribute row indices */
+    const float* attributes;      /* [Ba, Va, C], item stride attr_batch_stride in elements; 0 = shared, Ba = 1 */
+    long long attr_batch_stride;
+    float* internal;              /* the internal image [B, S, S, C]: written by the forward when non-null,
+                                     read by the backward for grad_vertices; or NULL */
+} NrAttributeArgs;
+/* sizeof(NrAttributeArgs), for bindings to check their mirror of the struct */
+NR_API size_t nr_attribute_args_size(void);
+/* images [B, C, s, s] contiguous, fully written; args->internal too when non-null. */
+NR_API int nr_attributes_forward(const NrAttributeArgs* args, float* images, void* stream);
+/* Scratch bytes of nr_attributes_backward: the per-face-corner records [B, F, 3, 3 + C] (zero-filled by
+ * the call). */
+NR_API size_t nr_attributes_backward_workspace_bytes(int batch_size, int num_faces, int num_channels);
+/* grad_images [B, C, s, s] contiguous -> grad_vertices [B, V, 3] and grad_attributes [Ba, Va, C] with
+ * Ba = attr_batch_stride ? B : 1 (the item sum for a shared table).  Either may be NULL; each one given is
+ * fully written.  grad_vertices needs args->internal (the forward's) and the vertex CSR: vertex_faces[
+ * vertex_offsets[v] .. vertex_offsets[v + 1]) lists 3 f + k for every faces[f, k] == v; grad_attributes
+ * needs the same lists of faces_attributes over the Va rows (attr_offsets [Va + 1], attr_faces [3 F]).
+ * A missing or short workspace is NR_ERR_WORKSPACE. */
+NR_API int nr_attributes_backward(const NrAttributeArgs* args, const float* grad_images, float* grad_vertices,
+                                  float* grad_attributes, const int32_t* vertex_offsets, const int32_t* vertex_faces,
+                                  const int32_t* attr_offsets, const int32_t* attr_faces, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
 /* Diagnostics (no reference counterpart): the kernels replace some IEEE divisions by a shortened
  * form of the compiler's own division sequence inside a guarded operand range (DESIGN.md,
  * "Numerics").  This runs both forms on n operand pairs so tests can check they agree bit for bit. */

@@ -22,5 +22,7 @@ from .mesh_loss import (FlattenLoss, LaplacianLoss, MeshTopology, flatten_loss, 
 from .image_loss import (HuberLoss, IoULoss, SquaredErrorLoss, huber_loss, huber_loss_torch, iou_loss, iou_loss_torch,
                          squared_error_loss, squared_error_loss_torch)
 from .optimizers import Adam, adam_step_torch
+from .attributes import (NR_ATTR_MAX_CHANNELS, attributes_from_maps_torch, rasterize_attributes,
+                         rasterize_attributes_torch)
 
 __version__ = '2.0.2+mi355x.1'

@@ -32,6 +32,7 @@ EXPORTS = [
     "nr_image_loss_workspace_bytes", "nr_pointwise_loss_forward", "nr_pointwise_loss_backward", "nr_iou_loss_forward",
     "nr_iou_loss_backward",
     "nr_adam_args_size", "nr_adam_scratch_bytes", "nr_adam_step",
+    "nr_attribute_args_size", "nr_attributes_forward", "nr_attributes_backward_workspace_bytes", "nr_attributes_backward",
 ]
 
 ABI_VERSION = 6  # include/nr_raster.h NR_ABI_VERSION
@@ -69,6 +70,7 @@ NR_LIGHT_AMBIENT, NR_LIGHT_DIRECTIONAL, NR_LIGHT_SPECULAR, NR_LIGHT_FLOATS = 0, 
 NR_CAMERA_NONE, NR_CAMERA_LOOK_AT, NR_CAMERA_LOOK = 0, 1, 2
 NR_LOSS_SQUARED, NR_LOSS_HUBER = 0, 1
 NR_ADAM_MAX_TENSORS, NR_ADAM_CHUNK = 24, 4096  # tensors per launch pair, elements of one tensor per block
+NR_ATTR_MAX_CHANNELS = 64
 
 
 class NrCameraArgs(ctypes.Structure):  # include/nr_raster.h
@@ -103,6 +105,15 @@ class NrAdamArgs(ctypes.Structure):  # include/nr_raster.h
     ]
 
 
+class NrAttributeArgs(ctypes.Structure):  # include/nr_raster.h
+    _fields_ = [
+        ("batch_size", c_int), ("num_faces", c_int), ("num_vertices", c_int), ("num_attributes", c_int),
+        ("num_channels", c_int), ("image_size", c_int), ("anti_aliasing", c_int), ("perspective_correct", c_int),
+        ("face_index", c_void_p), ("face_records", c_void_p), ("faces", c_void_p), ("faces_attributes", c_void_p),
+        ("attributes", c_void_p), ("attr_batch_stride", c_ll), ("internal", c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -114,7 +125,7 @@ def lib():
         raise RuntimeError("neural_renderer_v2_pytorch_amd: HIP library %s is missing; build it with "
                            "__graft_entry__.build() (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss and nr_adam_* entry points): a library built before them
+    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_adam_* and nr_attributes_* entry points): a library built before them
     # still reports the version this binding expects
     missing = [name for name in EXPORTS if not hasattr(L, name)]
     if missing:
@@ -172,6 +183,13 @@ def lib():
     L.nr_adam_scratch_bytes.restype = c_size_t
     L.nr_adam_scratch_bytes.argtypes = [c_int]
     L.nr_adam_step.argtypes = [ctypes.POINTER(NrAdamArgs), c_void_p]
+    L.nr_attribute_args_size.restype = c_size_t
+    L.nr_attribute_args_size.argtypes = []
+    L.nr_attributes_forward.argtypes = [ctypes.POINTER(NrAttributeArgs), c_void_p, c_void_p]
+    L.nr_attributes_backward_workspace_bytes.restype = c_size_t
+    L.nr_attributes_backward_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    L.nr_attributes_backward.argtypes = [ctypes.POINTER(NrAttributeArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
     L.nr_backward_workspace_bytes.restype = c_size_t
     L.nr_backward_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int]
     L.nr_raster_args_size.restype = c_size_t
@@ -189,7 +207,8 @@ def lib():
                         "nr_halo_bytes", "nr_raster_args_size", "nr_camera_workspace_bytes",
                         "nr_texture_packed_bytes", "nr_hot_acc_bytes", "nr_projection_args_size",
                         "nr_projection_workspace_bytes", "nr_mesh_loss_workspace_bytes",
-                        "nr_image_loss_workspace_bytes", "nr_adam_args_size", "nr_adam_scratch_bytes"):
+                        "nr_image_loss_workspace_bytes", "nr_adam_args_size", "nr_adam_scratch_bytes",
+                        "nr_attribute_args_size", "nr_attributes_backward_workspace_bytes"):
             getattr(L, name).restype = c_int
     # a library of another ABI revision (an NR_LIB_PATH override, a stale build) would misread the
     # arguments (e.g. an older nr_rasterize_backward takes its stream where workspace_zeroed is now)
@@ -201,6 +220,10 @@ def lib():
         raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has a %d-byte NrAdamArgs; this binding needs %d bytes "
                            "(rebuild with __graft_entry__.build())"
                            % (LIB_PATH, L.nr_adam_args_size(), ctypes.sizeof(NrAdamArgs)))
+    if L.nr_attribute_args_size() != ctypes.sizeof(NrAttributeArgs):
+        raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has a %d-byte NrAttributeArgs; this binding needs %d "
+                           "bytes (rebuild with __graft_entry__.build())"
+                           % (LIB_PATH, L.nr_attribute_args_size(), ctypes.sizeof(NrAttributeArgs)))
     if L.nr_version() != ABI_VERSION or L.nr_raster_args_size() != ctypes.sizeof(NrRasterArgs):
         raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has ABI version %d with a %d-byte NrRasterArgs; this "
                            "binding needs version %d and %d bytes (rebuild with __graft_entry__.build())"

@@ -26,7 +26,8 @@
 // halo cache, standalone reference kernels), nr_bwd.h (backward), nr_camera.h (look_at / look +
 // perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian and
 // flatten regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_adam.h
-// (multi-tensor Adam), nr_host.h (argument checks); this file holds the extern "C" ABI.
+// (multi-tensor Adam), nr_attributes.h (per-vertex attribute rendering), nr_host.h (argument checks); this file
+// holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -56,6 +57,7 @@
 #include "nr_mesh_loss.h"
 #include "nr_image_loss.h"
 #include "nr_adam.h"
+#include "nr_attributes.h"
 #include "nr_host.h"
 
 
@@ -1088,6 +1090,103 @@ int nr_adam_step(const NrAdamArgs* args, void* stream) {
         }
     }
     return NR_OK;
+}
+
+// ---- vertex attributes (nr_attributes.h) ----
+size_t nr_attribute_args_size(void) { return sizeof(NrAttributeArgs); }
+
+static int validate_attributes(const NrAttributeArgs* a) {
+    if (!a) return fail(NR_ERR_ARGS, "null attribute args");
+    if (a->batch_size < 0 || a->num_faces < 0 || a->num_vertices < 0 || a->num_attributes < 0 || a->image_size <= 0)
+        return fail(NR_ERR_ARGS, "bad sizes B=%d F=%d V=%d Va=%d s=%d", a->batch_size, a->num_faces, a->num_vertices,
+                    a->num_attributes, a->image_size);
+    if (a->image_size > 16384 || (a->anti_aliasing ? 2 * a->image_size : a->image_size) > 16384)
+        return fail(NR_ERR_ARGS, "image too large (s=%d)", a->image_size);
+    if (a->num_channels < 1 || a->num_channels > NR_ATTR_MAX_CHANNELS)
+        return fail(NR_ERR_ARGS, "bad channel count %d (1 .. %d)", a->num_channels, (int)NR_ATTR_MAX_CHANNELS);
+    if (a->batch_size > 65535) return fail(NR_ERR_ARGS, "too many items B=%d (at most 65535)", a->batch_size);
+    if (a->attr_batch_stride < 0) return fail(NR_ERR_ARGS, "negative attribute batch stride");
+    if ((long long)a->batch_size * a->num_vertices > INT_MAX || (long long)a->batch_size * a->num_attributes * a->num_channels > INT_MAX)
+        return fail(NR_ERR_ARGS, "too many vertices or attribute rows B=%d V=%d Va=%d", a->batch_size, a->num_vertices, a->num_attributes);
+    if (a->batch_size > 0 && a->num_faces > 0 && a->num_vertices > 0) {
+        if (!a->face_index || !a->face_records) return fail(NR_ERR_ARGS, "null face_index or face_records");
+        if (!a->faces_attributes || !a->attributes || a->num_attributes == 0)
+            return fail(NR_ERR_ARGS, "null or empty attributes / faces_attributes");
+    }
+    return NR_OK;
+}
+
+static bool attributes_empty(const NrAttributeArgs* a) { return a->batch_size == 0 || a->num_faces == 0 || a->num_vertices == 0; }
+
+int nr_attributes_forward(const NrAttributeArgs* a, float* images, void* stream) {
+    int e = validate_attributes(a);
+    if (e) return e;
+    if (a->batch_size == 0) return NR_OK;
+    if (!images) return fail(NR_ERR_ARGS, "null images");
+    hipStream_t st = (hipStream_t)stream;
+    const int s = a->image_size, S = a->anti_aliasing ? 2 * s : s, C = a->num_channels;
+    if (attributes_empty(a)) {  // nothing drawn: background everywhere
+        if (hipMemsetAsync(images, 0, (size_t)a->batch_size * C * s * s * 4, st) != hipSuccess ||
+            (a->internal && hipMemsetAsync(a->internal, 0, (size_t)a->batch_size * S * S * C * 4, st) != hipSuccess))
+            return check_launch("hipMemsetAsync");
+        return NR_OK;
+    }
+    const dim3 grid((unsigned)(((long long)s * s + AT_BLOCK - 1) / AT_BLOCK), (unsigned)a->batch_size);
+    if (a->anti_aliasing) nr_launch(k_attr_fwd<true>, grid, dim3(AT_BLOCK), 0, st, *a, S, images);
+    else nr_launch(k_attr_fwd<false>, grid, dim3(AT_BLOCK), 0, st, *a, S, images);
+    return check_launch("k_attr_fwd");
+}
+
+size_t nr_attributes_backward_workspace_bytes(int batch_size, int num_faces, int num_channels) {
+    if (batch_size <= 0 || num_faces <= 0 || num_channels <= 0) return 0;
+    return align_up((size_t)batch_size * num_faces * 3 * (3 + (size_t)num_channels) * 4);
+}
+
+int nr_attributes_backward(const NrAttributeArgs* a, const float* grad_images, float* grad_vertices, float* grad_attributes,
+                           const int32_t* vertex_offsets, const int32_t* vertex_faces, const int32_t* attr_offsets,
+                           const int32_t* attr_faces, void* workspace, size_t workspace_bytes, void* stream) {
+    int e = validate_attributes(a);
+    if (e) return e;
+    hipStream_t st = (hipStream_t)stream;
+    const int B = a->batch_size, F = a->num_faces, V = a->num_vertices, Va = a->num_attributes, C = a->num_channels;
+    const int Ba = a->attr_batch_stride ? B : 1;
+    const size_t nv = (size_t)B * V * 3, na = (size_t)Ba * Va * C;
+    if (attributes_empty(a)) {  // nothing drawn: zero gradients
+        if ((grad_vertices && nv && hipMemsetAsync(grad_vertices, 0, nv * 4, st) != hipSuccess) ||
+            (grad_attributes && na && hipMemsetAsync(grad_attributes, 0, na * 4, st) != hipSuccess))
+            return check_launch("hipMemsetAsync");
+        return NR_OK;
+    }
+    if (!grad_vertices && !grad_attributes) return NR_OK;
+    if (!grad_images) return fail(NR_ERR_ARGS, "null grad_images");
+    if (grad_vertices && (!a->internal || !vertex_offsets || !vertex_faces))
+        return fail(NR_ERR_ARGS, "grad_vertices needs the forward's internal image and the vertex CSR");
+    if (grad_attributes && (!attr_offsets || !attr_faces)) return fail(NR_ERR_ARGS, "grad_attributes needs the attribute CSR");
+    const size_t need = nr_attributes_backward_workspace_bytes(B, F, C);
+    if (!workspace || workspace_bytes < need) return fail(NR_ERR_WORKSPACE, "attribute backward workspace missing or too small");
+    if (hipMemsetAsync(workspace, 0, need, st) != hipSuccess) return check_launch("hipMemsetAsync");
+    float* rec = (float*)workspace;
+    const int S = a->anti_aliasing ? 2 * a->image_size : a->image_size;
+    const dim3 grid((unsigned)(((S + TW - 1) / TW) * ((S + TH - 1) / TH)), (unsigned)B);
+    if (grad_vertices && grad_attributes) nr_launch(k_attr_bwd<true, true>, grid, dim3(AT_BLOCK), 0, st, *a, S, grad_images, rec);
+    else if (grad_vertices) nr_launch(k_attr_bwd<true, false>, grid, dim3(AT_BLOCK), 0, st, *a, S, grad_images, rec);
+    else nr_launch(k_attr_bwd<false, true>, grid, dim3(AT_BLOCK), 0, st, *a, S, grad_images, rec);
+    e = check_launch("k_attr_bwd");
+    if (e) return e;
+    if (grad_vertices) {
+        const long long n = (long long)B * V;
+        nr_launch(k_attr_vertex_sum, dim3((unsigned)((n + AT_BLOCK - 1) / AT_BLOCK)), dim3(AT_BLOCK), 0, st, (const float*)rec,
+                  vertex_offsets, vertex_faces, grad_vertices, F, V, 3 + C, n);
+        e = check_launch("k_attr_vertex_sum");
+        if (e) return e;
+    }
+    if (grad_attributes) {
+        const long long n = (long long)na;
+        nr_launch(k_attr_row_sum, dim3((unsigned)((n + AT_BLOCK - 1) / AT_BLOCK)), dim3(AT_BLOCK), 0, st, (const float*)rec,
+                  attr_offsets, attr_faces, grad_attributes, B, F, Va, C, a->attr_batch_stride ? 0 : 1, n);
+        e = check_launch("k_attr_row_sum");
+    }
+    return e;
 }
 
 int nr_selftest_division(const float* a, const float* b, float* q_fast, float* q_ieee, long long n, void* stream) {

@@ -328,24 +328,18 @@ __device__ __forceinline__ float axis_grad(const float* Im, const float* I0, con
     return pick_grad(r_i + r_m, l_m + l_i);
 }
 
-__global__ void k_diff_bwd(const float* __restrict__ img, const float* __restrict__ grad, float* __restrict__ gxy, int H,
-                           int W, int C, float step, long long n) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const long long hw = (long long)H * W;
-    const int b = (int)(i / hw);
-    const int p = (int)(i % hw);
-    const int y = p / W, x = p % W;
-    auto at = [&](const float* base, int yy, int xx, int c) -> float {
-        return base[(((long long)b * H + yy) * W + xx) * C + c];
-    };
+// The stencil at pixel (y, x) of an H x W image with any number of channels: img(yy, xx, c) and
+// grad(yy, xx, c) read the saved image and its incoming gradient (k_diff_bwd: two arrays; k_attr_bwd,
+// nr_attributes.h: the gradient through the flip and the 2x2 mean of the output).
+template <typename ImgAt, typename GradAt>
+__device__ __forceinline__ void diff_stencil(ImgAt img, GradAt grad, int y, int x, int H, int W, int C, float step, float& gx,
+                                             float& gy) {
     // generic-C pair dots without local arrays
     auto dot = [&](int ya, int xa, int yb, int xb, int yg, int xg) -> float {
-        float s = (at(img, ya, xa, 0) - at(img, yb, xb, 0)) * at(grad, yg, xg, 0);
-        for (int c = 1; c < C; c++) s = s + (at(img, ya, xa, c) - at(img, yb, xb, c)) * at(grad, yg, xg, c);
+        float s = (img(ya, xa, 0) - img(yb, xb, 0)) * grad(yg, xg, 0);
+        for (int c = 1; c < C; c++) s = s + (img(ya, xa, c) - img(yb, xb, c)) * grad(yg, xg, c);
         return s;
     };
-    float gx, gy;
     {
         const bool hp = x <= W - 2, hm = x >= 1;
         const float r_i = hp ? -dot(y, x, y, x + 1, y, x + 1) / step : 0.f;
@@ -362,6 +356,22 @@ __global__ void k_diff_bwd(const float* __restrict__ img, const float* __restric
         const float l_m = hm ? -dot(y, x, y - 1, x, y - 1, x) / step : 0.f;
         gy = pick_grad(r_i + r_m, l_m + l_i);
     }
+}
+
+__global__ void k_diff_bwd(const float* __restrict__ img, const float* __restrict__ grad, float* __restrict__ gxy, int H,
+                           int W, int C, float step, long long n) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long long hw = (long long)H * W;
+    const int b = (int)(i / hw);
+    const int p = (int)(i % hw);
+    const int y = p / W, x = p % W;
+    auto at = [&](const float* base, int yy, int xx, int c) -> float {
+        return base[(((long long)b * H + yy) * W + xx) * C + c];
+    };
+    float gx, gy;
+    diff_stencil([&](int yy, int xx, int c) { return at(img, yy, xx, c); },
+                 [&](int yy, int xx, int c) { return at(grad, yy, xx, c); }, y, x, H, W, C, step, gx, gy);
     gxy[i * 2 + 0] = gx;
     gxy[i * 2 + 1] = gy;
 }

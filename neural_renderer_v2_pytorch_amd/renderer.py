@@ -2,6 +2,7 @@
 import math
 
 from . import camera
+from .attributes import rasterize_attributes
 from .look import look
 from .look_at import look_at
 from .perspective import perspective
@@ -80,6 +81,12 @@ class Renderer(object):
         params = RasterizeParam(vertices_textures=vertices_t, faces_textures=faces_t, textures=textures,
                                 background_color=self.background_color, backgrounds=backgrounds, lights=lights)
         return rasterize_rgb(vertices, faces, params, self._hyper())
+
+    def render_attributes(self, vertices, faces, attributes, faces_attributes=None, perspective_correct=True):
+        """Per-vertex attributes [B, V, C] (or a table shared by the batch) as an image [B, C, s, s]
+        (attributes.py): vertex colours, normal or position maps, labels, learned features."""
+        vertices = self.transform_vertices(vertices)
+        return rasterize_attributes(vertices, faces, attributes, self._hyper(), faces_attributes, perspective_correct)
 
     def render_depth(self, vertices, faces, backgrounds=None):
         vertices = self.transform_vertices(vertices)
