@@ -502,6 +502,55 @@ NR_API int nr_attributes_backward(const NrAttributeArgs* args, const float* grad
                                   const int32_t* attr_offsets, const int32_t* attr_faces, void* workspace,
                                   size_t workspace_bytes, void* stream);
 
+/* Point losses (point_loss.py; no reference counterpart): nearest neighbours and the chamfer distance
+ * between two point sets, and area-weighted surface sampling of a mesh.
+ *
+ * Chamfer: x [B, N, 3] contiguous, y [B, M, 3] with the item stride y_batch_stride in elements (0: one
+ * [M, 3] set shared by every item), directions = NR_CHAMFER_X_TO_Y | NR_CHAMFER_Y_TO_X.  The squared
+ * distance is fma(dz, dz, fma(dy, dy, dx dx)) of the float32 coordinate differences (never the
+ * |x|^2 + |y|^2 - 2 x.y expansion); the nearest neighbour is the lowest index among exact ties.
+ *   index_xy [B, N]: nearest y of every x;   index_yx [B, M]: nearest x of every y
+ *   loss_b = (1/N) sum_i |x_i - y_{index_xy[i]}|^2 + (1/M) sum_j |x_{index_yx[j]} - y_j|^2   (the requested terms)
+ * Backward, the indices held constant:
+ *   grad x_i = g_b [(2/N) (x_i - y_{index_xy[i]}) + (2/M) sum_{j: index_yx[j] = i} (x_i - y_j)],
+ *   grad y_j the same with the roles exchanged.
+ * No float atomics, every sum in one fixed order: bitwise reproducible.  The gathered sum of a point scans
+ * the other set's index array: eight equal ranges, each in ascending order, added in range order.
+ * Checked before any launch (NR_ERR_ARGS, also for a missing or short workspace): N, M >= 1, B <= 65535,
+ * B * max(N, M) <= INT_MAX - 4096, directions in 1..3, non-null pointers of what the directions need.  With B == 0
+ * nothing is launched. */
+enum { NR_CHAMFER_X_TO_Y = 1, NR_CHAMFER_Y_TO_X = 2 };
+/* Scratch bytes of nr_chamfer_forward (the per-point minima and, where the targets are split over several
+ * blocks, their partial (d2, j) pairs); 0 when a size is not positive. */
+NR_API size_t nr_chamfer_workspace_bytes(int batch_size, int num_x, int num_y, int directions);
+/* Writes the index array of every requested direction; dist2_xy [B, N] / dist2_yx [B, M] (the per-point
+ * squared distances) and loss [B] when non-null (one of them must be). */
+NR_API int nr_chamfer_forward(const float* x, const float* y, long long y_batch_stride, int batch_size, int num_x,
+                              int num_y, int directions, int32_t* index_xy, int32_t* index_yx, float* dist2_xy,
+                              float* dist2_yx, float* loss, void* workspace, size_t workspace_bytes, void* stream);
+/* grad_loss [B] -> grad_x [B, N, 3], grad_y [B, M, 3] (dense, also for a shared y); either may be NULL, each
+ * one given is fully written.  The index arrays are the forward's (trusted: every entry inside the other set). */
+NR_API int nr_chamfer_backward(const float* x, const float* y, long long y_batch_stride, const int32_t* index_xy,
+                               const int32_t* index_yx, const float* grad_loss, int batch_size, int num_x, int num_y,
+                               int directions, float* grad_x, float* grad_y, void* stream);
+/* Surface sampling: vertices [B, V, 3], faces [F, 3] (trusted: below V), u [B, S, 3] in [0, 1).  Per item,
+ * a_f = |(v1 - v0) x (v2 - v0)| / 2, c_f = the float32 inclusive prefix sum of a up to the latest face of
+ * positive area at or before f; sample s takes the smallest f with c_f > u_s0 c_{F-1} (if rounding leaves
+ * none: the last face of positive area), so a face of zero area is never taken; an item whose total area
+ * is 0 takes face F - 1.  weights = (1 - r, r (1 - u_s2), r u_s2) with r = sqrt(u_s1); point = the weighted
+ * sum of the face's corners.  Outputs points [B, S, 3], face [B, S], weights [B, S, 3], all fully written.
+ * Backward: grad_vertices [B, V, 3] (zero-filled by the call) += weights * grad_points at the corners,
+ * with float atomics (agrees from run to run up to the order of float additions).
+ * Checked before any launch (NR_ERR_ARGS, also for a missing or short workspace): S, F, V >= 1, B * S,
+ * B * F and 3 B V <= INT_MAX, non-null pointers. */
+NR_API size_t nr_sample_points_workspace_bytes(int batch_size, int num_faces);
+NR_API int nr_sample_points_forward(const float* vertices, const int32_t* faces, const float* u, int batch_size,
+                                    int num_vertices, int num_faces, int num_samples, float* points, int32_t* face,
+                                    float* weights, void* workspace, size_t workspace_bytes, void* stream);
+NR_API int nr_sample_points_backward(const int32_t* faces, const int32_t* face, const float* weights,
+                                     const float* grad_points, int batch_size, int num_vertices, int num_faces,
+                                     int num_samples, float* grad_vertices, void* stream);
+
 /* Diagnostics (no reference counterpart): the kernels replace some IEEE divisions by a shortened
  * form of the compiler's own division sequence inside a guarded operand range (DESIGN.md,
  * "Numerics").  This runs both forms on n operand pairs so tests can check they agree bit for bit. */
@@ -519,7 +568,7 @@ NR_API int nr_profile_enable(int on);
 NR_API int nr_profile_read(const char* kernel, float* ms);
 
 /* Launch record (no reference counterpart; the tests use it to assert which kernel variant ran).
- * For the most recent launch of `kernel` ("k_raster_fwd" or "k_raster_bwd") in this process
+ * For the most recent launch of `kernel` ("k_raster_fwd", "k_raster_bwd" or "k_chamfer_nn": 256 threads) in this process
  * (process-wide, like the profiling hook; torch issues a backward from its autograd thread): block_threads = threads per block (k_raster_fwd: 256 = four 16x16 quadrants per
  * 32x32 bin, 1024 = one wave per 8x8 block; k_raster_bwd: 256 = 2 pixels per lane, 512 = 1 pixel
  * per lane) and flags = NR_LAUNCH_* bits.  NR_ERR_ARGS when none was recorded. */
@@ -530,7 +579,9 @@ enum { NR_LAUNCH_FUSED_SHADE = 1, NR_LAUNCH_STATIC_CHANNELS = 2, NR_LAUNCH_TWO_P
        NR_LAUNCH_DEALT_QUARTERS = 64 /* k_raster_fwd: deep bins' 4x4 quarters dealt to the waves (not split) */,
        NR_LAUNCH_QUADRANTS = 128 /* k_raster_fwd: deep bins walked by four blocks, one per 16x16 quadrant (not split) */,
        /* k_raster_bwd: the feature instantiation (none of the three: the plain path) */
-       NR_LAUNCH_LIGHTS = 256, NR_LAUNCH_BACKGROUNDS = 512, NR_LAUNCH_SIL_ONLY = 1024 };
+       NR_LAUNCH_LIGHTS = 256, NR_LAUNCH_BACKGROUNDS = 512, NR_LAUNCH_SIL_ONLY = 1024,
+       /* k_chamfer_nn: the direction's targets were split over several blocks and combined */
+       NR_LAUNCH_SPLIT_X_TO_Y = 2048, NR_LAUNCH_SPLIT_Y_TO_X = 4096 };
 NR_API int nr_last_launch(const char* kernel, int* block_threads, int* flags);
 
 #ifdef NR_COUNT_TESTS

@@ -33,6 +33,8 @@ EXPORTS = [
     "nr_iou_loss_backward",
     "nr_adam_args_size", "nr_adam_scratch_bytes", "nr_adam_step",
     "nr_attribute_args_size", "nr_attributes_forward", "nr_attributes_backward_workspace_bytes", "nr_attributes_backward",
+    "nr_chamfer_workspace_bytes", "nr_chamfer_forward", "nr_chamfer_backward",
+    "nr_sample_points_workspace_bytes", "nr_sample_points_forward", "nr_sample_points_backward",
 ]
 
 ABI_VERSION = 6  # include/nr_raster.h NR_ABI_VERSION
@@ -40,6 +42,7 @@ ABI_VERSION = 6  # include/nr_raster.h NR_ABI_VERSION
 NR_LAUNCH_FUSED_SHADE, NR_LAUNCH_STATIC_CHANNELS, NR_LAUNCH_TWO_PX_PER_LANE, NR_LAUNCH_DEEP_FIRST, NR_LAUNCH_SPLIT = 1, 2, 4, 8, 16
 NR_LAUNCH_HOT_WINDOWS, NR_LAUNCH_DEALT_QUARTERS, NR_LAUNCH_QUADRANTS = 32, 64, 128
 NR_LAUNCH_LIGHTS, NR_LAUNCH_BACKGROUNDS, NR_LAUNCH_SIL_ONLY = 256, 512, 1024  # k_raster_bwd's feature instantiation
+NR_LAUNCH_SPLIT_X_TO_Y, NR_LAUNCH_SPLIT_Y_TO_X = 2048, 4096  # k_chamfer_nn: a direction's targets split over several blocks
 NR_HOT_MAX, NR_HOT_COPIES = 256, 32
 
 c_int, c_float, c_void_p, c_size_t, c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong
@@ -71,6 +74,8 @@ NR_CAMERA_NONE, NR_CAMERA_LOOK_AT, NR_CAMERA_LOOK = 0, 1, 2
 NR_LOSS_SQUARED, NR_LOSS_HUBER = 0, 1
 NR_ADAM_MAX_TENSORS, NR_ADAM_CHUNK = 24, 4096  # tensors per launch pair, elements of one tensor per block
 NR_ATTR_MAX_CHANNELS = 64
+NR_CHAMFER_X_TO_Y, NR_CHAMFER_Y_TO_X = 1, 2
+NR_CHAMFER_TILE = 1024  # csrc/nr_point_loss.h PL_TILE: targets staged in LDS at a time
 
 
 class NrCameraArgs(ctypes.Structure):  # include/nr_raster.h
@@ -125,7 +130,7 @@ def lib():
         raise RuntimeError("neural_renderer_v2_pytorch_amd: HIP library %s is missing; build it with "
                            "__graft_entry__.build() (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_adam_* and nr_attributes_* entry points): a library built before them
+    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_adam_*, nr_attributes_* and point-loss entry points): a library built before them
     # still reports the version this binding expects
     missing = [name for name in EXPORTS if not hasattr(L, name)]
     if missing:
@@ -190,6 +195,17 @@ def lib():
     L.nr_attributes_backward_workspace_bytes.argtypes = [c_int, c_int, c_int]
     L.nr_attributes_backward.argtypes = [ctypes.POINTER(NrAttributeArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
+    L.nr_chamfer_workspace_bytes.restype = c_size_t
+    L.nr_chamfer_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    L.nr_chamfer_forward.argtypes = [c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_size_t, c_void_p]
+    L.nr_chamfer_backward.argtypes = [c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                      c_void_p, c_void_p]
+    L.nr_sample_points_workspace_bytes.restype = c_size_t
+    L.nr_sample_points_workspace_bytes.argtypes = [c_int, c_int]
+    L.nr_sample_points_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_size_t, c_void_p]
+    L.nr_sample_points_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
     L.nr_backward_workspace_bytes.restype = c_size_t
     L.nr_backward_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int]
     L.nr_raster_args_size.restype = c_size_t
@@ -208,7 +224,8 @@ def lib():
                         "nr_texture_packed_bytes", "nr_hot_acc_bytes", "nr_projection_args_size",
                         "nr_projection_workspace_bytes", "nr_mesh_loss_workspace_bytes",
                         "nr_image_loss_workspace_bytes", "nr_adam_args_size", "nr_adam_scratch_bytes",
-                        "nr_attribute_args_size", "nr_attributes_backward_workspace_bytes"):
+                        "nr_attribute_args_size", "nr_attributes_backward_workspace_bytes",
+                        "nr_chamfer_workspace_bytes", "nr_sample_points_workspace_bytes"):
             getattr(L, name).restype = c_int
     # a library of another ABI revision (an NR_LIB_PATH override, a stale build) would misread the
     # arguments (e.g. an older nr_rasterize_backward takes its stream where workspace_zeroed is now)
@@ -234,8 +251,8 @@ def lib():
 
 
 def last_launch(kernel):
-    """(threads per block, NR_LAUNCH_* flags) of the latest launch of `kernel` ("k_raster_fwd" or
-    "k_raster_bwd") in this process: the variant the library actually ran."""
+    """(threads per block, NR_LAUNCH_* flags) of the latest launch of `kernel` ("k_raster_fwd",
+    "k_raster_bwd" or "k_chamfer_nn") in this process: the variant the library actually ran."""
     t, f = c_int(), c_int()
     check(lib().nr_last_launch(kernel.encode(), ctypes.byref(t), ctypes.byref(f)), "nr_last_launch")
     return t.value, f.value

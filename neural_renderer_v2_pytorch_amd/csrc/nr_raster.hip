@@ -26,8 +26,8 @@
 // halo cache, standalone reference kernels), nr_bwd.h (backward), nr_camera.h (look_at / look +
 // perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian and
 // flatten regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_adam.h
-// (multi-tensor Adam), nr_attributes.h (per-vertex attribute rendering), nr_host.h (argument checks); this file
-// holds the extern "C" ABI.
+// (multi-tensor Adam), nr_attributes.h (per-vertex attribute rendering), nr_point_loss.h (chamfer distance,
+// nearest points and surface sampling), nr_host.h (argument checks); this file holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -58,6 +58,7 @@
 #include "nr_image_loss.h"
 #include "nr_adam.h"
 #include "nr_attributes.h"
+#include "nr_point_loss.h"
 #include "nr_host.h"
 
 
@@ -895,6 +896,189 @@ int nr_flatten_backward(const float* records, const int32_t* edge_offsets, const
     return check_launch("k_flat_bwd_gather");
 }
 
+// ---- point losses (nr_point_loss.h) ----
+// How one direction of a chamfer launch is cut: query blocks per item, and target ranges per query block
+// (more than one -- the split path -- while the direction has fewer than PL_SPLIT_BLOCKS blocks and every
+// range still holds at least a full tile of targets: few queries against many targets would otherwise
+// leave most of the chip idle).
+struct PlPlan {
+    int nqb, nsplit;
+};
+static PlPlan pl_plan(int B, int nq, int nt) {
+    PlPlan p;
+    p.nqb = (int)(((long long)nq + PL_QBLOCK - 1) / PL_QBLOCK);
+    const long long have = (long long)B * p.nqb;
+    const long long want = (PL_SPLIT_BLOCKS + have - 1) / have, most = nt / PL_TILE;
+    p.nsplit = (int)(want < most ? want : most);
+    if (p.nsplit < 1) p.nsplit = 1;
+    return p;
+}
+// workspace floats of one direction: the per-query minima [B, nq] and, on the split path, the partial
+// (d2, j) pairs [B, nsplit, nq] twice
+static size_t pl_dir_bytes(int B, int nq, int nt) {
+    const PlPlan p = pl_plan(B, nq, nt);
+    return align_up((size_t)B * nq * 4) + (p.nsplit > 1 ? 2 * align_up((size_t)B * p.nsplit * nq * 4) : 0);
+}
+
+static int validate_chamfer(int B, int N, int M, int directions) {
+    if (B < 0) return fail(NR_ERR_ARGS, "bad batch size B=%d", B);
+    if (N <= 0 || M <= 0) return fail(NR_ERR_ARGS, "empty point set N=%d M=%d (both must be at least 1)", N, M);
+    if (directions < 1 || directions > 3) return fail(NR_ERR_ARGS, "bad directions %d (1 x_to_y, 2 y_to_x, 3 both)", directions);
+    if (B > 65535) return fail(NR_ERR_ARGS, "too many items B=%d (at most 65535)", B);
+    if ((long long)B * (N > M ? N : M) > INT_MAX - 4096) return fail(NR_ERR_ARGS, "too many points B=%d N=%d M=%d", B, N, M);
+    return NR_OK;
+}
+
+size_t nr_chamfer_workspace_bytes(int batch_size, int num_x, int num_y, int directions) {
+    if (batch_size <= 0 || num_x <= 0 || num_y <= 0) return 0;
+    return ((directions & NR_CHAMFER_X_TO_Y) ? pl_dir_bytes(batch_size, num_x, num_y) : 0) +
+           ((directions & NR_CHAMFER_Y_TO_X) ? pl_dir_bytes(batch_size, num_y, num_x) : 0);
+}
+
+int nr_chamfer_forward(const float* x, const float* y, long long y_batch_stride, int batch_size, int num_x, int num_y,
+                       int directions, int32_t* index_xy, int32_t* index_yx, float* dist2_xy, float* dist2_yx, float* loss,
+                       void* workspace, size_t workspace_bytes, void* stream) {
+    const int B = batch_size, N = num_x, M = num_y;
+    int e = validate_chamfer(B, N, M, directions);
+    if (e) return e;
+    if (y_batch_stride < 0) return fail(NR_ERR_ARGS, "negative y batch stride");
+    if (B == 0) return NR_OK;
+    if (!x || !y) return fail(NR_ERR_ARGS, "null x or y");
+    const bool xy = directions & NR_CHAMFER_X_TO_Y, yx = directions & NR_CHAMFER_Y_TO_X;
+    if ((xy && !index_xy) || (yx && !index_yx)) return fail(NR_ERR_ARGS, "null index output of a requested direction");
+    if (!loss && !(xy && dist2_xy) && !(yx && dist2_yx)) return fail(NR_ERR_ARGS, "null loss and no dist2 output");
+    if (!workspace || workspace_bytes < nr_chamfer_workspace_bytes(B, N, M, directions))
+        return fail(NR_ERR_ARGS, "chamfer workspace missing or too small");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    PlDir d[2] = {};
+    float* fin_d[2] = {nullptr, nullptr};
+    int32_t* fin_j[2] = {nullptr, nullptr};
+    int nd = 0, flags = 0;
+    for (int k = 0; k < 2; k++) {
+        if (!(k == 0 ? xy : yx)) continue;
+        const int nq = k == 0 ? N : M, nt = k == 0 ? M : N;
+        const PlPlan p = pl_plan(B, nq, nt);
+        PlDir& r = d[nd];
+        r.q = k == 0 ? x : y, r.t = k == 0 ? y : x;
+        r.q_stride = k == 0 ? (long long)N * 3 : y_batch_stride;
+        r.t_stride = k == 0 ? y_batch_stride : (long long)N * 3;
+        r.nq = nq, r.nt = nt, r.nqb = p.nqb, r.nsplit = p.nsplit;
+        float* user = k == 0 ? dist2_xy : dist2_yx;
+        fin_d[nd] = user ? user : (float*)ws;
+        ws += align_up((size_t)B * nq * 4);
+        fin_j[nd] = k == 0 ? index_xy : index_yx;
+        if (p.nsplit > 1) {
+            const size_t part = align_up((size_t)B * p.nsplit * nq * 4);
+            r.dist2 = (float*)ws, r.index = (int32_t*)(ws + part);
+            ws += 2 * part;
+            flags |= k == 0 ? NR_LAUNCH_SPLIT_X_TO_Y : NR_LAUNCH_SPLIT_Y_TO_X;
+        } else {
+            r.dist2 = fin_d[nd], r.index = fin_j[nd];
+        }
+        nd++;
+    }
+    const int blocks0 = d[0].nqb * d[0].nsplit, blocks1 = nd > 1 ? d[1].nqb * d[1].nsplit : 0;
+    if (nd == 1) d[1] = d[0];
+    nr_launch(k_chamfer_nn, dim3((unsigned)(blocks0 + blocks1), (unsigned)B), dim3(PL_BLOCK), 0, st, d[0], d[1], blocks0);
+    g_last_chamfer.store(LaunchRec{PL_BLOCK, flags});
+    e = check_launch("k_chamfer_nn");
+    if (e) return e;
+    for (int k = 0; k < nd; k++) {
+        if (d[k].nsplit == 1) continue;
+        nr_launch(k_chamfer_combine, dim3((unsigned)((d[k].nq + PL_BLOCK - 1) / PL_BLOCK), (unsigned)B), dim3(PL_BLOCK), 0, st,
+                  (const float*)d[k].dist2, (const int32_t*)d[k].index, d[k].nq, d[k].nsplit, fin_d[k], fin_j[k]);
+        e = check_launch("k_chamfer_combine");
+        if (e) return e;
+    }
+    if (!loss) return NR_OK;
+    const float* sxy = xy ? fin_d[0] : nullptr;
+    const float* syx = yx ? fin_d[xy ? 1 : 0] : nullptr;
+    nr_launch(k_chamfer_sum, dim3((unsigned)B), dim3(PL_WIDE), 0, st, sxy, N, syx, M, loss);
+    return check_launch("k_chamfer_sum");
+}
+
+int nr_chamfer_backward(const float* x, const float* y, long long y_batch_stride, const int32_t* index_xy, const int32_t* index_yx,
+                        const float* grad_loss, int batch_size, int num_x, int num_y, int directions, float* grad_x, float* grad_y,
+                        void* stream) {
+    const int B = batch_size, N = num_x, M = num_y;
+    int e = validate_chamfer(B, N, M, directions);
+    if (e) return e;
+    if (y_batch_stride < 0) return fail(NR_ERR_ARGS, "negative y batch stride");
+    if (B == 0 || (!grad_x && !grad_y)) return NR_OK;
+    if (!x || !y || !grad_loss) return fail(NR_ERR_ARGS, "null x, y or grad_loss");
+    const bool xy = directions & NR_CHAMFER_X_TO_Y, yx = directions & NR_CHAMFER_Y_TO_X;
+    if ((xy && !index_xy) || (yx && !index_yx)) return fail(NR_ERR_ARGS, "null index array of a requested direction");
+    PlSide s[2] = {};
+    int ns = 0;
+    if (grad_x) {
+        PlSide& r = s[ns++];
+        r.p = x, r.o = y, r.p_stride = (long long)N * 3, r.o_stride = y_batch_stride, r.np = N, r.no = M;
+        r.own = xy ? index_xy : nullptr, r.other = yx ? index_yx : nullptr, r.grad = grad_x;
+        r.nblk = (N + 63) / 64;
+    }
+    if (grad_y) {
+        PlSide& r = s[ns++];
+        r.p = y, r.o = x, r.p_stride = y_batch_stride, r.o_stride = (long long)N * 3, r.np = M, r.no = N;
+        r.own = yx ? index_yx : nullptr, r.other = xy ? index_xy : nullptr, r.grad = grad_y;
+        r.nblk = (M + 63) / 64;
+    }
+    const int blocks0 = s[0].nblk, blocks1 = ns > 1 ? s[1].nblk : 0;
+    if (ns == 1) s[1] = s[0];
+    nr_launch(k_chamfer_bwd, dim3((unsigned)(blocks0 + blocks1), (unsigned)B), dim3(PL_BWD_BLOCK), 0, (hipStream_t)stream, s[0], s[1],
+              blocks0, grad_loss);
+    return check_launch("k_chamfer_bwd");
+}
+
+static int validate_sample_points(int B, int V, int F, int S) {
+    if (B < 0 || V < 0) return fail(NR_ERR_ARGS, "bad sizes B=%d V=%d", B, V);
+    if (S <= 0) return fail(NR_ERR_ARGS, "no samples S=%d (must be at least 1)", S);
+    if (F <= 0 || V == 0) return fail(NR_ERR_ARGS, "no faces to sample F=%d V=%d", F, V);
+    if ((long long)B * S > INT_MAX || (long long)B * F > INT_MAX || (long long)B * V > INT_MAX / 3)
+        return fail(NR_ERR_ARGS, "too many samples, faces or vertices B=%d S=%d F=%d V=%d", B, S, F, V);
+    return NR_OK;
+}
+
+size_t nr_sample_points_workspace_bytes(int batch_size, int num_faces) {
+    if (batch_size <= 0 || num_faces <= 0) return 0;
+    return align_up((size_t)batch_size * num_faces * 4);
+}
+
+int nr_sample_points_forward(const float* vertices, const int32_t* faces, const float* u, int batch_size, int num_vertices,
+                             int num_faces, int num_samples, float* points, int32_t* face, float* weights, void* workspace,
+                             size_t workspace_bytes, void* stream) {
+    const int B = batch_size, V = num_vertices, F = num_faces, S = num_samples;
+    int e = validate_sample_points(B, V, F, S);
+    if (e) return e;
+    if (B == 0) return NR_OK;
+    if (!vertices || !faces || !u || !points || !face || !weights) return fail(NR_ERR_ARGS, "null pointer");
+    if (!workspace || workspace_bytes < nr_sample_points_workspace_bytes(B, F))
+        return fail(NR_ERR_ARGS, "sample_points workspace missing or too small");
+    hipStream_t st = (hipStream_t)stream;
+    nr_launch(k_sample_scan, dim3((unsigned)B), dim3(PL_WIDE), 0, st, vertices, faces, V, F, (float*)workspace);
+    e = check_launch("k_sample_scan");
+    if (e) return e;
+    const long long n = (long long)B * S;
+    nr_launch(k_sample_points, dim3((unsigned)((n + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, st, vertices, faces, u,
+              (const float*)workspace, V, F, S, n, points, face, weights);
+    return check_launch("k_sample_points");
+}
+
+int nr_sample_points_backward(const int32_t* faces, const int32_t* face, const float* weights, const float* grad_points,
+                              int batch_size, int num_vertices, int num_faces, int num_samples, float* grad_vertices, void* stream) {
+    const int B = batch_size, V = num_vertices, F = num_faces, S = num_samples;
+    int e = validate_sample_points(B, V, F, S);
+    if (e) return e;
+    if (B == 0) return NR_OK;
+    if (!faces || !face || !weights || !grad_points || !grad_vertices) return fail(NR_ERR_ARGS, "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(grad_vertices, 0, (size_t)B * V * 3 * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");
+    const long long n = (long long)B * S;
+    nr_launch(k_sample_points_bwd, dim3((unsigned)((n + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, st, faces, face, weights,
+              grad_points, V, S, n, grad_vertices);
+    return check_launch("k_sample_points_bwd");
+}
+
 // ---- image losses (nr_image_loss.h) ----
 static long long il_chunks(int n) { return ((long long)n + IL_CHUNK - 1) / IL_CHUNK; }
 
@@ -1226,7 +1410,8 @@ __attribute__((visibility("default"))) int nr_debug_bwd_timing(unsigned long lon
 int nr_last_launch(const char* kernel, int* block_threads, int* flags) {
     if (!kernel || !block_threads || !flags) return fail(NR_ERR_ARGS, "null argument");
     const LaunchSlot* slot = strcmp(kernel, "k_raster_fwd") == 0 ? &g_last_fwd
-                             : strcmp(kernel, "k_raster_bwd") == 0 ? &g_last_bwd : nullptr;
+                             : strcmp(kernel, "k_raster_bwd") == 0 ? &g_last_bwd
+                             : strcmp(kernel, "k_chamfer_nn") == 0 ? &g_last_chamfer : nullptr;
     if (!slot) return fail(NR_ERR_ARGS, "nr_last_launch: unknown kernel name %s", kernel);
     const LaunchRec r = slot->load();
     if (!r.threads) return fail(NR_ERR_ARGS, "nr_last_launch: no %s launch recorded in this process", kernel);

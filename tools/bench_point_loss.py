@@ -1,0 +1,188 @@
+"""Times the point losses, forward + backward: chamfer_distance (both directions, gradient to x) between
+two jittered copies of a mesh's vertices, and sample_points (S = 10000, gradient to the vertices), each on
+the icosphere L4 (V 2562, F 5120, B 64) and the torus (V 25000, F 50000, B 1): the fused path against
+the torch composition on the same float32 GPU tensors, each eager and as a torch.cuda.CUDAGraph replay.
+
+Every (cell, path) runs in a child process of its own under `timeout`; the first one that fails ends the
+run.  Per cell: eager wall-clock per step (host time of a synchronised loop), eager GPU time per step
+(events around each step), graph-replay GPU time per step, and the peak device memory of the eager loop.
+The JSON lines go to --out (default profiles/point_loss_bench.jsonl) and to stdout; the last line holds
+the acceptance cells (fused not slower than the composition), the pair rate of the fused chamfer cells
+(both directions: 2 B N M pairs per step over the graph-replay time, which also holds the backward), each
+kernel's algorithmic bytes and the registers the compiler reports for it.
+
+    python tools/bench_point_loss.py [--steps 100] [--warmup 20] [--out FILE]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = {"ico4_b64": ("ico4", 64), "torus_b1": ("torus", 1)}
+CELLS = [("chamfer", s) for s in SHAPES] + [("sample", s) for s in SHAPES]
+PATHS = ("fused", "composition")
+SAMPLES = 10000
+# VGPRs per lane of each kernel as hipcc reports them for gfx950 (-Rpass-analysis=kernel-resource-usage on
+# csrc/nr_raster.hip with the build's flags); 78 allocates 80: 6 waves per SIMD, the rest run at 8
+KERNEL_VGPRS = {"k_chamfer_nn": 78, "k_chamfer_combine": 10, "k_chamfer_sum": 18, "k_chamfer_bwd": 32,
+                "k_sample_scan": 56, "k_sample_points": 26, "k_sample_points_bwd": 19}
+
+
+def mesh(kind):
+    from neural_renderer_v2_pytorch_amd import synthetic
+    return synthetic.torus() if kind == "torus" else synthetic.icosphere(4)
+
+
+def kernel_bytes(B, N, M, F, S):
+    """Algorithmic bytes of each fused kernel: every array read or written once (4-byte elements; the
+    split path's partials and the targets' re-reads by further blocks are not counted)."""
+    return {
+        "k_chamfer_nn": 4 * (2 * B * (N + M) * 3 + 2 * B * (N + M)),
+        "k_chamfer_sum": 4 * (B * (N + M) + B),
+        "k_chamfer_bwd(grad x)": 4 * (B * (N + M) * 3 + B * (N + M) + B * N * 3 + B),
+        "k_sample_scan": 4 * (B * F * 3 * 3 + F * 3 + B * F),
+        "k_sample_points": 4 * (B * S * (3 + 3 + 1 + 3) + B * S * 9),
+        "k_sample_points_bwd": 4 * (B * S * (3 + 1 + 3 + 3) + B * S * 9),
+    }
+
+
+def cell(what, shape, path, warmup, steps):
+    import numpy as np
+    import torch
+    import neural_renderer_v2_pytorch_amd as nr
+    from neural_renderer_v2_pytorch_amd import synthetic
+
+    kind, B = SHAPES[shape]
+    dev = torch.device("cuda:0")
+    v, f = mesh(kind)
+    V, F = int(v.shape[0]), int(f.shape[0])
+    faces = torch.as_tensor(f, device=dev)
+    x = torch.as_tensor(synthetic.jittered(v, B, sigma=0.005), device=dev).requires_grad_(True)
+    if what == "chamfer":
+        y = torch.as_tensor(synthetic.jittered(v, B, sigma=0.005, seed_base=2000), device=dev)
+        g = torch.as_tensor(np.random.RandomState(0).normal(size=B).astype(np.float32), device=dev)
+        fn = nr.chamfer_distance if path == "fused" else nr.chamfer_distance_torch
+    else:
+        u = torch.as_tensor(np.random.RandomState(1).uniform(0, 1, (B, SAMPLES, 3)).astype(np.float32), device=dev)
+        g = torch.as_tensor(np.random.RandomState(0).normal(size=(B, SAMPLES, 3)).astype(np.float32), device=dev)
+        fn = nr.sample_points if path == "fused" else nr.sample_points_torch
+
+    def note(msg):
+        print("[%s %s %s] %s" % (what, shape, path, msg), file=sys.stderr, flush=True)
+
+    def step():
+        # returns a detached result: no reference to the autograd graph outlives a step (bench_mesh_loss.py)
+        x.grad = None
+        out = fn(x, y) if what == "chamfer" else fn(x, faces, SAMPLES, u=u)
+        out.backward(g)
+        return out.detach()
+
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(warmup):
+            step()
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    note("warm-up done")
+    graph = torch.cuda.CUDAGraph()
+    x.grad = None
+    with torch.cuda.graph(graph):
+        gout = step()
+    ggrad = x.grad
+    note("captured")
+    for _ in range(warmup):
+        graph.replay()
+    torch.cuda.synchronize()
+    reps = []
+    for _ in range(5):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(steps):
+            graph.replay()
+        b.record()
+        torch.cuda.synchronize()
+        reps.append(a.elapsed_time(b) / steps)
+    graph_out, graph_grad = gout.clone(), ggrad.clone()
+    note("replayed")
+
+    starts = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
+    ends = [torch.cuda.Event(enable_timing=True) for _ in range(steps)]
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    t0 = time.perf_counter()
+    for i in range(steps):
+        starts[i].record()
+        eager_out = step()
+        ends[i].record()
+    torch.cuda.synchronize()
+    wall = (time.perf_counter() - t0) / steps * 1e3
+    gpu = float(np.median([a.elapsed_time(b) for a, b in zip(starts, ends)]))
+    peak = torch.cuda.max_memory_allocated() - base
+    note("eager done")
+    # the sampling backward adds with float atomics: its gradient is compared to a tolerance, not bitwise
+    if what == "chamfer":
+        same = bool(torch.equal(graph_out, eager_out) and torch.equal(graph_grad, x.grad))
+    else:
+        same = bool(torch.equal(graph_out, eager_out) and torch.allclose(graph_grad, x.grad, rtol=1e-4, atol=1e-6))
+    return {"cell": what, "shape": shape, "path": path, "B": B, "N": V, "M": V, "F": F, "S": SAMPLES if what == "sample" else 0,
+            "eager_wall_ms": round(wall, 4), "eager_gpu_ms": round(gpu, 4), "graph_ms": round(float(np.median(reps)), 4),
+            "graph_ms_min": round(min(reps), 4), "peak_step_bytes": int(peak), "graph_equals_eager": same,
+            "out": [float(t) for t in eager_out.reshape(-1)[:2]], "device": torch.cuda.get_device_name(0)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "point_loss_bench.jsonl"))
+    ap.add_argument("--timeout", type=int, default=240, help="seconds per cell")
+    ap.add_argument("--cell", nargs=3, metavar=("WHAT", "SHAPE", "PATH"), help="run one cell in this process")
+    a = ap.parse_args()
+    if a.cell:
+        print(json.dumps(cell(a.cell[0], a.cell[1], a.cell[2], a.warmup, a.steps)))
+        return 0
+    rows = {}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as out:
+        for what, shape in CELLS:
+            for path in PATHS:
+                cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--steps", str(a.steps),
+                       "--warmup", str(a.warmup), "--cell", what, shape, path]
+                p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
+                if p.returncode != 0:
+                    print("cell %s %s %s ended with status %d: stopping" % (what, shape, path, p.returncode), file=sys.stderr)
+                    return p.returncode
+                line = p.stdout.strip().splitlines()[-1]
+                rows[(what, shape, path)] = json.loads(line)
+                out.write(line + "\n")
+                out.flush()
+                print(line, flush=True)
+        summary = {"summary": {}, "pairs_per_s": {}, "peak_step_bytes": {}, "kernel_bytes": {}, "kernel_vgprs": KERNEL_VGPRS}
+        for what, shape in CELLS:
+            fused, comp = rows[(what, shape, "fused")], rows[(what, shape, "composition")]
+            name = "%s/%s" % (what, shape)
+            for mode in ("eager_gpu_ms", "eager_wall_ms", "graph_ms"):
+                summary["summary"]["%s/%s" % (name, mode)] = {
+                    "fused": fused[mode], "composition": comp[mode],
+                    "speedup": round(comp[mode] / fused[mode], 2), "not_slower": fused[mode] <= comp[mode]}
+            summary["peak_step_bytes"][name] = {"fused": fused["peak_step_bytes"], "composition": comp["peak_step_bytes"]}
+            if what == "chamfer":
+                summary["pairs_per_s"][name] = round(2.0 * fused["B"] * fused["N"] * fused["M"] / (fused["graph_ms"] * 1e-3), 1)
+                summary["kernel_bytes"][shape] = kernel_bytes(fused["B"], fused["N"], fused["M"], fused["F"], SAMPLES)
+        line = json.dumps(summary)
+        out.write(line + "\n")
+        print(line)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
