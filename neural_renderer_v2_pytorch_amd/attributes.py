@@ -29,7 +29,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .rasterize import _faces_i32, _vertex_adjacency
+from .topology import faces_i32, vertex_adjacency
 from .rasterize_param import RasterizeHyperparam
 
 NR_ATTR_MAX_CHANNELS = _lib.NR_ATTR_MAX_CHANNELS
@@ -102,12 +102,12 @@ def _prepare(vertices, faces, attributes, hyperparams, faces_attributes, perspec
     c.near, c.far = float(hp.near), float(hp.far)
     c.pc = bool(perspective_correct)
     dev = vertices.device
-    c.faces = _faces_i32(faces, dev, c.V, "faces")
+    c.faces = faces_i32(faces, dev, c.V, "faces")
     c.F = c.faces.shape[0]
     if faces_attributes is None:
-        c.faces_attributes = c.faces if c.Va == c.V else _faces_i32(faces, dev, c.Va, "faces (as faces_attributes)")
+        c.faces_attributes = c.faces if c.Va == c.V else faces_i32(faces, dev, c.Va, "faces (as faces_attributes)")
     else:
-        c.faces_attributes = _faces_i32(faces_attributes, dev, c.Va, "faces_attributes")
+        c.faces_attributes = faces_i32(faces_attributes, dev, c.Va, "faces_attributes")
         if c.faces_attributes.shape[0] != c.F:
             raise ValueError("faces_attributes must have one row per face (%d), got %d" % (c.F, c.faces_attributes.shape[0]))
     _lib.require_gpu(vertices, attributes)
@@ -174,8 +174,8 @@ class RasterizeAttributes(torch.autograd.Function):
         if want_v or want_a:
             # the CSR lists of the backward's second level, built once per index tensor (a host copy on the
             # first sight of a tensor; cached, so steady-state steps never synchronise)
-            vadj = _vertex_adjacency(c.faces, c.V) if want_v else None
-            aadj = _vertex_adjacency(c.faces_attributes, c.Va) if want_a else None
+            vadj = vertex_adjacency(c.faces, c.V) if want_v else None
+            aadj = vertex_adjacency(c.faces_attributes, c.Va) if want_a else None
             ctx.save_for_backward(attributes)  # read again by the perspective-correct depth gradient
             ctx.state = (a, fim, frec, internal, vadj, aadj)
             ctx.internal_bytes = internal.numel() * 4 if internal is not None else 0

@@ -18,119 +18,11 @@ vertex index are ignored by both losses; duplicate faces count separately.
 The topology (mesh_topology) is built on the host once per faces tensor and cached, so steady-state
 calls issue no host synchronisation and a step can be captured in a HIP graph.  The fused kernels use
 no float atomics: losses and gradients are bitwise identical from run to run."""
-import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .rasterize import _TensorCache, _faces_i32
-
-class MeshTopology:
-    """What both losses need of a faces tensor, as int32 tensors on one device:
-      nbr_offsets [V + 1], nbr_index   CSR vertex -> its distinct neighbours, ascending
-      edges [E2, 4]                    rows (v0, v1, v2, v3) of the two-face edges, sorted by (v0, v1)
-      edge_offsets [V + 1], edge_slots [4 E2]
-                                       CSR vertex -> the entries 4 e + k with edges[e, k] == vertex, ascending
-    and the counts num_vertices, num_edges (E2), num_boundary_edges (one incident face) and
-    num_nonmanifold_edges (three or more)."""
-    FIELDS = ("nbr_offsets", "nbr_index", "edges", "edge_offsets", "edge_slots")
-
-    def __init__(self, tensors, num_vertices, num_boundary_edges, num_nonmanifold_edges):
-        for name, t in zip(self.FIELDS, tensors):
-            setattr(self, name, t)
-        self.num_vertices = int(num_vertices)
-        self.num_edges = int(self.edges.shape[0])
-        self.num_boundary_edges = int(num_boundary_edges)
-        self.num_nonmanifold_edges = int(num_nonmanifold_edges)
-        self._on = {self.device: self}
-        self._index = None
-
-    @property
-    def device(self):
-        return self.edges.device
-
-    def __iter__(self):
-        return iter(getattr(self, name) for name in self.FIELDS)
-
-    def to(self, device):
-        """This topology on `device` (copied once per device)."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        hit = self._on.get(device)
-        if hit is None:
-            hit = MeshTopology([t.to(device) for t in self], self.num_vertices, self.num_boundary_edges,
-                               self.num_nonmanifold_edges)
-            hit._on = self._on
-            self._on[device] = hit
-        return hit
-
-    def composition_index(self):
-        """int64 index tensors of the torch composition: the row and column of every neighbour entry,
-        the neighbour counts, and the edge rows."""
-        if self._index is None:
-            deg = (self.nbr_offsets[1:] - self.nbr_offsets[:-1]).long()
-            rows = torch.repeat_interleave(torch.arange(self.num_vertices, device=self.device), deg)
-            self._index = (rows, self.nbr_index.long(), deg, self.edges.long())
-        return self._index
-
-
-def _build_topology(faces, V):
-    """The five arrays of MeshTopology (int32 numpy) and the boundary / non-manifold edge counts, from
-    faces [F, 3] with indices in [0, V).  Stable sorts throughout: every list has one fixed order."""
-    f = np.asarray(faces, np.int64).reshape(-1, 3)
-    f = f[(f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2])]
-    # distinct neighbours: every face edge in both directions, duplicates dropped (np.unique sorts)
-    src = np.concatenate([f[:, 0], f[:, 1], f[:, 1], f[:, 2], f[:, 2], f[:, 0]])
-    dst = np.concatenate([f[:, 1], f[:, 0], f[:, 2], f[:, 1], f[:, 0], f[:, 2]])
-    pair = np.unique(src * V + dst)
-    nbr_offsets = np.zeros(V + 1, np.int64)
-    if V:
-        np.cumsum(np.bincount(pair // V, minlength=V), out=nbr_offsets[1:])
-    nbr_index = pair % V if V else pair
-    # undirected edges: corner k of a face is opposite the edge of its two other corners; face-major
-    # order and a stable sort keep each edge's faces in ascending face order
-    a, b, opp = f[:, [1, 2, 0]].reshape(-1), f[:, [2, 0, 1]].reshape(-1), f.reshape(-1)
-    key = np.minimum(a, b) * V + np.maximum(a, b)
-    order = np.argsort(key, kind="stable")
-    uniq, start, count = np.unique(key[order], return_index=True, return_counts=True)
-    two = count == 2
-    first = start[two]
-    edges = np.stack([uniq[two] // max(V, 1), uniq[two] % max(V, 1), opp[order[first]], opp[order[first + 1]]], 1).reshape(-1, 4)
-    if 4 * edges.shape[0] >= 2 ** 31 or pair.shape[0] >= 2 ** 31:
-        raise ValueError("mesh too large: 4 * E2 and the neighbour count must stay below 2^31")
-    flat = edges.reshape(-1)
-    edge_slots = np.argsort(flat, kind="stable")
-    edge_offsets = np.zeros(V + 1, np.int64)
-    if V:
-        np.cumsum(np.bincount(flat, minlength=V), out=edge_offsets[1:])
-    arrays = [x.astype(np.int32) for x in (nbr_offsets, nbr_index, edges, edge_offsets, edge_slots)]
-    return arrays, int((count == 1).sum()), int((count > 2).sum())
-
-
-_topologies = _TensorCache()
-
-
-def mesh_topology(faces, num_vertices, device=None):
-    """The MeshTopology of faces [F, 3] (any integer tensor or array; indices outside [0, num_vertices)
-    raise IndexError) on `device` (default: the faces' own, the CPU for arrays).  Built on the host once
-    per (faces storage, version, shape, num_vertices, device) and cached: calls that pass the same
-    device int32 tensor again issue no host synchronisation."""
-    V = int(num_vertices)
-    if V < 0:
-        raise ValueError("num_vertices must not be negative")
-    if device is None:
-        device = faces.device if torch.is_tensor(faces) else torch.device("cpu")
-    device = torch.device(device)
-    f = _faces_i32(faces, device, V, "faces")
-    key = (f.data_ptr(), f._version, f.shape[0], V, f.device)
-    hit = _topologies.get(key)
-    if hit is not None:
-        return hit[0]
-    arrays, boundary, nonmanifold = _build_topology(f.cpu().numpy(), V)
-    topo = MeshTopology([torch.as_tensor(x, device=f.device) for x in arrays], V, boundary, nonmanifold)
-    _topologies.put(key, (topo, f))  # keep f alive: its storage is the key
-    return topo
+from .topology import MeshTopology, mesh_topology
 
 
 def _prepare(vertices, faces):

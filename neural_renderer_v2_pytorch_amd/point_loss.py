@@ -31,7 +31,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .mesh_loss import _finish
-from .rasterize import _faces_i32
+from .topology import faces_i32
 
 CHAMFER_TILE = _lib.NR_CHAMFER_TILE  # targets the nearest-neighbour kernel stages in LDS at a time
 _DIRECTIONS = {"both": _lib.NR_CHAMFER_X_TO_Y | _lib.NR_CHAMFER_Y_TO_X, "x_to_y": _lib.NR_CHAMFER_X_TO_Y,
@@ -130,7 +130,7 @@ def _prepare_mesh(vertices, faces, num_samples, u, generator):
     B, V, S = v.shape[0], v.shape[1], int(num_samples)
     if S < 1:
         raise ValueError("num_samples must be at least 1, got %d" % S)
-    f = _faces_i32(faces, v.device, V, "faces")
+    f = faces_i32(faces, v.device, V, "faces")
     if f.shape[0] == 0:
         raise ValueError("sample_points needs at least one face")
     if u is None:

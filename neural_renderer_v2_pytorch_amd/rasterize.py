@@ -27,6 +27,7 @@ import torch
 
 from . import _lib
 from .rasterize_param import RasterizeParam, RasterizeHyperparam  # noqa: F401  (re-exported like the reference)
+from .topology import TensorCache, faces_i32, normal_adjacency, vertex_adjacency
 
 
 # ------------------------------------------------------------------------------------------------
@@ -117,93 +118,7 @@ def mask_foreground(data, face_index_map):
 
 # ------------------------------------------------------------------------------------------------
 # the fused path
-class _TensorCache:
-    """Small LRU of results derived from device index tensors (the faces checks and the vertex
-    adjacency), keyed by (storage address, version counter, shape, ...).  Each entry keeps its
-    source tensor alive, so its storage -- hence the address in the key -- cannot be freed and
-    reused by another tensor while the entry lives; the version counter catches in-place edits.
-    A caller alternating a few meshes (several objects, or train / validation sets) keeps hitting:
-    no device-to-host copy and no host sync per call, so such steps stay graph-capturable."""
-
-    def __init__(self, size=8):
-        import collections
-        self.size = size
-        self.entries = collections.OrderedDict()
-
-    def get(self, key):
-        hit = self.entries.get(key)
-        if hit is not None:
-            self.entries.move_to_end(key)
-        return hit
-
-    def put(self, key, value):
-        self.entries[key] = value
-        self.entries.move_to_end(key)
-        while len(self.entries) > self.size:
-            self.entries.popitem(last=False)
-
-
-_faces_checked = _TensorCache()
-
-
-def _faces_i32(faces, device, bound, what):
-    """[F,3] int32 on `device`, indices checked like the reference's IndexError on out-of-range
-    indices (rasterize.py:232, :246).  CPU index tensors are checked on the host before the copy;
-    device-resident int32 ones once per (storage, version), so steady-state calls never sync."""
-    f = faces if isinstance(faces, torch.Tensor) else torch.as_tensor(faces)
-    if f.ndim != 2 or f.shape[1] != 3:
-        raise AssertionError("%s must be [F, 3]" % what)
-    if f.is_cuda and f.dtype == torch.int32 and f.device == device and f.is_contiguous():
-        # the steady-state case (a device int32 index tensor reused every step): no conversion calls
-        key = (f.data_ptr(), f._version, f.shape[0], bound, f.device)
-        if f.numel() and _faces_checked.get(key) is None:
-            lo, hi = int(f.min()), int(f.max())
-            if lo < 0 or hi >= bound:
-                raise IndexError("%s index out of range [0, %d): min %d max %d" % (what, bound, lo, hi))
-            _faces_checked.put(key, f)
-        return f
-    if not f.is_cuda:
-        if f.numel():
-            lo, hi = int(f.min()), int(f.max())
-            if lo < 0 or hi >= bound:
-                raise IndexError("%s index out of range [0, %d): min %d max %d" % (what, bound, lo, hi))
-        return f.to(dtype=torch.int32).contiguous().to(device, non_blocking=False)
-    reuse = f.dtype == torch.int32 and f.is_contiguous() and f.device == device
-    f = f.to(device=device, dtype=torch.int32).contiguous()
-    key = (f.data_ptr(), f._version, f.shape[0], bound, f.device)
-    if f.numel() and not (reuse and _faces_checked.get(key) is not None):
-        lo, hi = int(f.min()), int(f.max())
-        if lo < 0 or hi >= bound:
-            raise IndexError("%s index out of range [0, %d): min %d max %d" % (what, bound, lo, hi))
-        if reuse:
-            _faces_checked.put(key, f)
-    return f
-
-
-_adjacency = _TensorCache()
-
-
-def _vertex_adjacency(faces_i32, V):
-    """CSR vertex -> face corners (3 f + k) for the backward's vertex gather, built on the host
-    with a stable sort (deterministic summation order) and cached per (storage, version)."""
-    key = (faces_i32.data_ptr(), faces_i32._version, faces_i32.shape[0], V, faces_i32.device)
-    hit = _adjacency.get(key)
-    if hit is not None:
-        return hit[0], hit[1]
-    import numpy as np
-    flat = faces_i32.reshape(-1).cpu().numpy().astype(np.int64)
-    order = np.argsort(flat, kind="stable").astype(np.int32)
-    counts = np.bincount(flat, minlength=V)
-    offsets = np.zeros(V + 1, np.int32)
-    np.cumsum(counts, out=offsets[1:])
-    off = torch.as_tensor(offsets, device=faces_i32.device)
-    ent = torch.as_tensor(order, device=faces_i32.device)
-    _adjacency.put(key, (off, ent, faces_i32))  # keep faces_i32 alive: its storage is the key
-    return off, ent
-
-
-_normal_adj = _TensorCache()
-_hot_cache = _TensorCache()
+_hot_cache = TensorCache()
 # a texture window shared by at least this many faces gets private copies in the backward
 # (NrRasterArgs.face_hot): every face of an OBJ's flat-colour material samples one 2x2 atlas patch
 # (load_obj.py:84-94), so all the waves that render the material add into the same texels
@@ -216,11 +131,10 @@ def _face_hot(ft, vt_src, dev):
     (bit for bit, so the backward computes the same texel window for all of them) form a group; the
     NR_HOT_MAX largest groups of at least _HOT_MIN_FACES faces get ids 0.., every other face -1.
     (None, 0) when no group qualifies.  Cached per (storage, version) of both tensors."""
-    key = (ft.data_ptr(), ft._version, vt_src.data_ptr(), vt_src._version, tuple(ft.shape), tuple(vt_src.shape),
-           _HOT_MIN_FACES, dev)
+    key = TensorCache.key(ft, TensorCache.key(vt_src, (_HOT_MIN_FACES, dev)))
     hit = _hot_cache.get(key)
     if hit is not None:
-        return hit[0], hit[1]
+        return hit
     if vt_src.is_cuda and torch.cuda.is_current_stream_capturing():
         return None, 0  # the grouping needs a host copy; the plain flush is exact without it
     import numpy as np
@@ -239,28 +153,8 @@ def _face_hot(ft, vt_src, dev):
             ids = np.full(len(cnt), -1, np.int32)
             ids[big] = np.arange(len(big), dtype=np.int32)
             res = (torch.as_tensor(ids[inv], device=dev), len(big))
-    _hot_cache.put(key, (res[0], res[1], ft, vt_src))  # keep the key tensors alive
-    return res[0], res[1]
-
-
-def _normal_adjacency(faces_i32, V):
-    """CSR vertex -> its distinct faces, ascending (the one-hot [F, V] matrix of
-    rasterize.py:173-179: a face counts once per vertex), cached per faces tensor."""
-    key = (faces_i32.data_ptr(), faces_i32._version, faces_i32.shape[0], V, faces_i32.device)
-    hit = _normal_adj.get(key)
-    if hit is not None:
-        return hit[0], hit[1]
-    import numpy as np
-    f = faces_i32.cpu().numpy().astype(np.int64)
-    F = f.shape[0]
-    pairs = np.unique(np.stack([f.reshape(-1), np.repeat(np.arange(F), 3)], 1), axis=0)  # sorted by (v, f)
-    counts = np.bincount(pairs[:, 0], minlength=V)
-    offsets = np.zeros(V + 1, np.int32)
-    np.cumsum(counts, out=offsets[1:])
-    off = torch.as_tensor(offsets, device=faces_i32.device)
-    ent = torch.as_tensor(pairs[:, 1].astype(np.int32), device=faces_i32.device)
-    _normal_adj.put(key, (off, ent, faces_i32))
-    return off, ent
+    _hot_cache.put(key, res, ft, vt_src)
+    return res
 
 
 def _light_records(lights, B, dev):
@@ -505,7 +399,7 @@ class Rasterize(torch.autograd.Function):
             arena[lay.halo:lay.halo + lay.halo_bytes].view(torch.float32).fill_(_HALO_FILL)
         light = None
         if light_recs is not None:
-            nadj = _normal_adjacency(faces, cfg.V)
+            nadj = normal_adjacency(faces, cfg.V)
             a.num_lights = nl
             a.lights = light_recs.data_ptr()
             a.normal_offsets, a.normal_faces = nadj[0].data_ptr(), nadj[1].data_ptr()
@@ -575,7 +469,7 @@ class Rasterize(torch.autograd.Function):
         else:
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
             ws_ptr = ws.data_ptr()
-        adj = _vertex_adjacency(faces, cfg.V)
+        adj = vertex_adjacency(faces, cfg.V)
         a.vertex_offsets, a.vertex_faces = adj[0].data_ptr(), adj[1].data_ptr()
         gbg = None
         if backgrounds is not None and rgb:
@@ -657,7 +551,7 @@ def rasterize_core(vertices, faces, params: RasterizeParam, hyperparams: Rasteri
     cfg.C = (3 if flags & _lib.NR_DRAW_RGB else 0) + (1 if flags & _lib.NR_DRAW_SILHOUETTES else 0) + \
         (1 if flags & _lib.NR_DRAW_DEPTH else 0)  # nr_num_channels
     cfg.want_fim = bool(return_face_index)
-    fi = _faces_i32(faces_t, dev, cfg.V, "faces")
+    fi = faces_i32(faces_t, dev, cfg.V, "faces")
     tex = vt = ft = None
     cfg.tex_shared = cfg.vt_shared = False
     cfg.tex_hw = (0, 0)
@@ -679,7 +573,7 @@ def rasterize_core(vertices, faces, params: RasterizeParam, hyperparams: Rasteri
             vt = vt.contiguous()
         cfg.Vt = vt.shape[1]
         cfg.vt_shared = vt.shape[0] == 1 and cfg.B > 1
-        ft = _faces_i32(params.faces_textures, dev, cfg.Vt, "faces_textures")
+        ft = faces_i32(params.faces_textures, dev, cfg.Vt, "faces_textures")
         if ft.shape[0] != cfg.F:
             raise AssertionError("faces_textures must have one row per face")
         if tex.dtype != torch.float32:

@@ -1283,8 +1283,8 @@ def test_backward_workspace_zeroed_by_forward(dev):
 
 
 def test_two_meshes_alternating_in_one_hip_graph(dev):
-    """Faces checks and adjacencies are cached per faces tensor in a small LRU (rasterize.py
-    _TensorCache): a caller alternating two meshes pays the host-side checks once per mesh, never
+    """Faces checks and adjacencies are cached per faces tensor in a small LRU (topology.py
+    TensorCache): a caller alternating two meshes pays the host-side checks once per mesh, never
     per call.  Proof that no call syncs with the host: after one eager step per mesh, a step that
     renders and differentiates mesh A, then mesh B, then A again is captured in ONE HIP graph
     (a device-to-host copy or a .cpu() inside the capture would raise) and replayed; the replayed
@@ -1329,7 +1329,7 @@ def test_two_meshes_alternating_in_one_hip_graph(dev):
         assert torch.equal(a, b)
     for (pv, _), ge in zip(meshes, eager_g):
         close_grads(pv.grad, ge, "graph grad vertices")
-    assert len(nrr._faces_checked.entries) >= 2 and len(nrr._adjacency.entries) >= 2
+    assert len(nr.topology.faces_checked.entries) >= 2 and len(nr.topology.adjacency.entries) >= 2
 
 
 def test_car_renderer_render_batch(oracle_mod, dev):

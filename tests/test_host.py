@@ -245,22 +245,6 @@ def test_edge_cull_is_exact_on_host(tmp_path):
     assert m and int(m.group(3)) == 0 and int(m.group(2)) > int(m.group(1)) // 4, out.stdout
 
 
-def test_tensor_cache_lru():
-    """rasterize._TensorCache: a small LRU keyed by (storage, version, ...); hits refresh an
-    entry, the least recently used entry leaves first, and entries keep their source alive."""
-    from neural_renderer_v2_pytorch_amd.rasterize import _TensorCache
-    c = _TensorCache(size=2)
-    a, b, d = torch.zeros(3), torch.ones(3), torch.full((3,), 2.0)
-    ka, kb, kd = [(t.data_ptr(), t._version) for t in (a, b, d)]
-    c.put(ka, a)
-    c.put(kb, b)
-    assert c.get(ka) is a       # refreshes a: b is now the oldest
-    c.put(kd, d)
-    assert c.get(kb) is None and c.get(ka) is a and c.get(kd) is d
-    a.add_(1)                   # an in-place edit bumps the version: a new key
-    assert c.get((a.data_ptr(), a._version)) is None
-
-
 def test_pixel_centre_is_exact_on_host(tmp_path):
     """csrc/nr_pixel.h (the kernels' pixel centre without doubles: an f32 division, or a 2^-k scaling
     for a power-of-two raster) equals the reference's (float)((2.0 * i + 1 - S) / S)

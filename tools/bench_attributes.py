@@ -61,7 +61,7 @@ def cell(shape, path, warmup, steps, reps):
     import torch
     import neural_renderer_v2_pytorch_amd as nr
     from neural_renderer_v2_pytorch_amd import _lib, synthetic
-    from neural_renderer_v2_pytorch_amd.rasterize import _vertex_adjacency
+    from neural_renderer_v2_pytorch_amd.topology import vertex_adjacency
 
     mesh, B, s, C = SHAPES[shape]
     dev = torch.device("cuda:0")
