@@ -24,6 +24,18 @@ def grid_fin():
     return v, np.asarray(faces, np.int32)
 
 
+def grid(n):
+    """An n x n height-field patch over [-0.5, 0.5]^2, heights 0.05 sin(2 pi x) cos(3 pi y) (slopes below
+    0.5: neither flat nor folded), every cell split into two triangles: V n^2, F 2 (n - 1)^2, and
+    3 (n - 1)^2 - 2 (n - 1) edges with two faces."""
+    c = np.linspace(-0.5, 0.5, n)
+    x, y = np.meshgrid(c, c, indexing="xy")
+    v = np.stack([x, y, 0.05 * np.sin(2 * math.pi * x) * np.cos(3 * math.pi * y)], -1).reshape(-1, 3)
+    a = (np.arange(n - 1)[:, None] * n + np.arange(n - 1)[None, :]).reshape(-1)
+    f = np.concatenate([np.stack([a, a + 1, a + n + 1], 1), np.stack([a, a + n + 1, a + n], 1)])
+    return v, f.astype(np.int32)
+
+
 def hinge(phi):
     """Two unit-sized triangles on the shared edge (0, 1); the opposite vertices 2 and 3 stand at the
     angle phi about that edge (phi = pi: flat)."""

@@ -4,7 +4,10 @@ float64 on the CPU.
 Tolerances are test_gpu_mesh_loss's: losses rtol = atol = 1e-5, gradients 1e-4 of the reference gradient's
 largest magnitude plus 1e-4 relative.  On these inputs (images uniform in [0, 1), targets 0 / 1 or uniform,
 weights uniform in [0, 2), upstream gradient N(0, 1) per item) float32 torch on the CPU stays under 1 % of
-both tolerances against float64, so the reference alone is well inside them."""
+both tolerances against float64, so the reference alone is well inside them; that holds for the shapes of
+more than 256 chunks per item too (many_chunks: 0.4 % of the loss and 0.2 % of the gradient tolerance,
+many_chunks_odd: 0.7 % and 0.2 %) and for wrap_small and wrap_straddle (0.8 % and 0.2 %); wrap_small_chunks
+uses 1.1 % of the loss tolerance (Huber, full weights) and 0.2 % of the gradient's."""
 import functools
 
 import numpy as np
@@ -25,7 +28,23 @@ SHAPES = {
     "tail": (2, 3, 5, 7),       # N = 105: a scalar tail; mask period 35: scalar weight loads
     "odd": (3, 1, 67, 67),      # N = 4489, odd: items 1 and 2 are not 16-byte aligned; two chunks, the last partial
     "aligned": (2, 5, 64, 64),  # N = 20480: five full chunks per item, five channels sharing a mask
+    # vector weight loads that wrap: a mask period of 240 is below the 1024 elements between a lane's loads, so
+    # every lane's offset advances by 1024 % 240 = 64 per load and wraps.  N = 720 is less than those 1024
+    # elements: only a lane's first load counts, at an offset of i0 % period in the second and third period
+    "wrap_small": (2, 3, 12, 20),
+    # the same period with N = 4800: one full chunk, where all four loads of a lane count and their offsets
+    # wrap at different loads from lane to lane, and a partial one that starts inside a period (4096 % 240 = 16)
+    "wrap_small_chunks": (2, 20, 12, 20),
+    # N = 11520, mask period 2304: chunks 1 and 2 start inside a period, and a lane's later loads cross its end
+    "wrap_straddle": (2, 5, 48, 48),
+    # more than 256 partials per item, so the second stage's strided loop takes a second trip:
+    # N = 1310720 is 320 chunks on the vector path (mask period 262144)
+    "many_chunks": (2, 5, 512, 512),
+    # N = 1050625 is 257 chunks, the last partial; N is odd, so item 1 is off 16 bytes: the scalar path
+    "many_chunks_odd": (2, 1, 1025, 1025),
 }
+# the weight forms a shape runs with, where not all of them (the large shapes: the float64 reference costs)
+FORMS = {"many_chunks": ("none", "shared_mask"), "many_chunks_odd": ("none", "shared_mask")}
 # (fused, composition, extra arguments) -- the targets are binary for IoU, uniform otherwise
 LOSSES = {
     "squared": (nr.squared_error_loss, nr.squared_error_loss_torch, ()),
@@ -86,7 +105,7 @@ def case(name):
     d = draw(SHAPES[name], sum(map(ord, name)))
     ref = {}
     for loss in LOSSES:
-        for form in WEIGHTS if loss != "iou" else ("none",):
+        for form in FORMS.get(name, WEIGHTS) if loss != "iou" else ("none",):
             ref[loss, form] = reference(loss, d["x"], d["tb" if loss == "iou" else "t"], weights_of(d, form), d["g"])
     return d, ref
 
@@ -104,10 +123,10 @@ def fused(loss, x, t, w, g, **kw):
 
 
 COMBOS = [(loss, form) for loss in LOSSES for form in (WEIGHTS if loss != "iou" else ("none",))]
+NAMED_COMBOS = [(name, loss, form) for loss, form in COMBOS for name in SHAPES if form in FORMS.get(name, WEIGHTS)]
 
 
-@pytest.mark.parametrize("loss,form", COMBOS)
-@pytest.mark.parametrize("name", list(SHAPES))
+@pytest.mark.parametrize("name,loss,form", NAMED_COMBOS)
 def test_fused_matches_float64(dev, name, loss, form):
     d, ref = case(name)
     x, t, w, g = (to_dev(a, dev) for a in (d["x"], d["tb" if loss == "iou" else "t"], weights_of(d, form), d["g"]))
@@ -227,6 +246,36 @@ def test_weight_forms_are_bit_identical(dev, name, loss):
         for form, w in forms:
             again = fused(loss, x, t, w, g)
             assert torch.equal(first[0], again[0]) and torch.equal(first[1], again[1]), (kind, form)
+
+
+def off_sixteen(w):
+    """The values of the contiguous float32 tensor w as a view that starts one float into a buffer one float
+    longer: w's own base is on 16 bytes (asserted), the view's is 4 past them."""
+    buf = torch.empty(w.numel() + 1, dtype=w.dtype, device=w.device)
+    view = buf[1:1 + w.numel()].view(w.shape)
+    view.copy_(w)
+    assert w.is_contiguous() and view.is_contiguous() and torch.equal(view, w)
+    assert w.data_ptr() % 16 == 0 and view.data_ptr() % 16 == 4, (w.data_ptr() % 16, view.data_ptr() % 16)
+    return view
+
+
+@pytest.mark.parametrize("loss", ["squared", "huber"])
+def test_vector_weights_equal_scalar_weights_bitwise(dev, loss):
+    """Weights whose base is on 16 bytes take 16-byte loads at an offset that advances and wraps per load;
+    the same values one float off 16 bytes take scalar loads at i % period in the same lanes and order.  The
+    mask's H * W is a multiple of 4 at all these shapes, so the base alone decides: loss and gradient must
+    be bit for bit the same, through wrapping periods (the wrap shapes) as without (aligned)."""
+    for name in ("wrap_small", "wrap_small_chunks", "wrap_straddle", "aligned"):
+        d, _ = case(name)
+        x, t, g = to_dev(d["x"], dev), to_dev(d["t"], dev), to_dev(d["g"], dev)
+        assert x.data_ptr() % 16 == 0 and t.data_ptr() % 16 == 0 and (x.shape[2] * x.shape[3]) % 4 == 0
+        for form in ("mask", "shared_mask"):
+            w = to_dev(weights_of(d, form), dev).contiguous()
+            vector = fused(loss, x, t, w, g)
+            scalar = fused(loss, x, t, off_sixteen(w), g)
+            assert vector[1].data_ptr() % 16 == 0 and scalar[1].data_ptr() % 16 == 0
+            assert torch.equal(vector[0], scalar[0]) and torch.equal(vector[1], scalar[1]), (name, form)
+            close_out(vector[0], case(name)[1][loss, form][0], "%s %s %s" % (name, loss, form))
 
 
 @pytest.mark.parametrize("loss", list(LOSSES))

@@ -33,8 +33,14 @@ CASES = {  # name: (B, N, M)
     "blocks_tiles": (2, 1025, 2049),  # several query blocks; CHAMFER_TILE lies strictly inside M and N + 1
     "one_x": (2, 1, 40),
     "one_y": (2, 40, 1),
+    # more than two target ranges per query block (the cases above split in two at most): the remainder goes
+    # to the first ranges, and the combine walks past its first step
+    # (none of these five queries chooses the middle range: test_every_target_range_holds_a_nearest_point does)
+    "three_ranges": (1, 5, 3074),   # 3 ranges of 1025, 1025, 1024 targets; smallest relative gap 1.4e-4
+    "five_ranges": (2, 3, 5123),    # 5 ranges, the first 3 one target longer; smallest relative gap 2.6e-4
 }
-SPLIT = {"few_x": _lib.NR_LAUNCH_SPLIT_X_TO_Y, "few_y": _lib.NR_LAUNCH_SPLIT_Y_TO_X}
+SPLIT = {"few_x": _lib.NR_LAUNCH_SPLIT_X_TO_Y, "few_y": _lib.NR_LAUNCH_SPLIT_Y_TO_X,
+         "three_ranges": _lib.NR_LAUNCH_SPLIT_X_TO_Y, "five_ranges": _lib.NR_LAUNCH_SPLIT_X_TO_Y}
 
 
 def close_grads(a, b, what):
@@ -112,7 +118,7 @@ def test_nearest_points_match_float64(dev, name):
         print("%s %s: dist2 max relative error %.3g" % (name, key, float(err)))
         assert float(err) <= DIST_RTOL
     if name in SPLIT:
-        q, t = (x, y) if name == "few_x" else (y, x)
+        q, t = (x, y) if SPLIT[name] == _lib.NR_LAUNCH_SPLIT_X_TO_Y else (y, x)
         nr.nearest_points(q.to(dev), t.to(dev))
         assert _lib.last_launch("k_chamfer_nn") == (256, _lib.NR_LAUNCH_SPLIT_X_TO_Y)
 
@@ -129,7 +135,7 @@ def test_chamfer_matches_float64(dev, name, directions):
     close_out(loss, want, "%s %s" % (name, directions))
     close_grads(gx, want_gx, "%s %s grad x" % (name, directions))
     close_grads(gy, want_gy, "%s %s grad y" % (name, directions))
-    if name in SPLIT and directions != ("y_to_x" if name == "few_x" else "x_to_y"):
+    if name in SPLIT and directions != ("y_to_x" if SPLIT[name] == _lib.NR_LAUNCH_SPLIT_X_TO_Y else "x_to_y"):
         assert threads == 256 and flags & SPLIT[name], (threads, flags)  # the few-against-many direction ran split
     if name == "wave":
         assert flags == 0  # small sets: no split
@@ -190,12 +196,81 @@ def test_duplicated_targets_pick_the_lowest_index(dev):
     assert _lib.last_launch("k_chamfer_nn")[1] & _lib.NR_LAUNCH_SPLIT_X_TO_Y
     want = nr.nearest_points_torch(x.double(), y2.double())[1]
     assert int(idx.max()) < 1250 and torch.equal(idx.cpu(), want)
+    # 3075 targets, 1025 repeated three times against 5 queries: three ranges of 1025, so every tie spans all
+    # three partials of the combine
+    x, y = points(2, 5, 1025)
+    assert relative_gap(x.double(), y.double()) > GAP
+    y3 = torch.cat([y, y, y], 1)
+    d2, idx = nr.nearest_points(x.to(dev), y3.to(dev))
+    assert _lib.last_launch("k_chamfer_nn")[1] & _lib.NR_LAUNCH_SPLIT_X_TO_Y
+    want = nr.nearest_points_torch(x.double(), y3.double())[1]
+    assert int(idx.max()) < 1025 and torch.equal(idx.cpu(), want)
+    assert torch.equal(idx.cpu(), nr.nearest_points_torch(x.double(), y.double())[1])
+    x, y = points(2, 70, 1250)
     # within one block: targets 3 and 9 equal
     y3 = y[:, :40].clone()
     y3[:, 9] = y3[:, 3]
     q = torch.cat([x[:, :5], y3[:, 9:10] + 1e-3], 1)
     idx = nr.nearest_points(q.to(dev), y3.to(dev))[1]
     assert idx[:, 5].tolist() == [3, 3] and not bool((idx == 9).any())
+
+
+@pytest.mark.parametrize("name", ["three_ranges", "five_ranges"])
+def test_every_target_range_holds_a_nearest_point(dev, name):
+    """With the file's draw no query of three_ranges has its nearest target in the middle range, so a combine
+    that skipped a partial would pass there.  Here the queries sit 1e-3 beside the first and the last target of
+    every range (n equal shares of M, the remainder one each to the first ranges): each partial wins for two
+    queries, and a range boundary off by one would lose or double one of these targets."""
+    _, y, _, _ = case(name)
+    B, M = y.shape[0], y.shape[1]
+    n = {"three_ranges": 3, "five_ranges": 5}[name]
+    share, rem = divmod(M, n)
+    los = [s * share + min(s, rem) for s in range(n + 1)]
+    assert los[-1] == M and 0 < rem < n
+    picks = torch.as_tensor([j for s in range(n) for j in (los[s], los[s + 1] - 1)])
+    q = (y[:, picks] + torch.as_tensor([1e-3, -1e-3, 1e-3])).contiguous()
+    want_d2, want = nr.nearest_points_torch(q.double(), y.double())
+    assert torch.equal(want.long(), picks[None].expand(B, -1)) and relative_gap(q.double(), y.double()) > GAP
+    d2, idx = nr.nearest_points(q.to(dev), y.to(dev))
+    assert _lib.last_launch("k_chamfer_nn")[1] & _lib.NR_LAUNCH_SPLIT_X_TO_Y
+    assert torch.equal(idx.cpu(), want), (idx.cpu().tolist(), picks.tolist())
+    assert float(((d2.cpu().double() - want_d2).abs() / want_d2).max()) <= DIST_RTOL
+
+
+@pytest.mark.parametrize("name", ["partial_block", "three_ranges"])
+def test_nearest_points_with_nan_coordinates(dev, name):
+    """The saved indices stay inside the other set whatever the coordinates hold: a distance to or from a
+    NaN compares false, so a NaN query keeps the first target of its range (index 0 after the combine too),
+    a NaN target is never chosen, and no other point's result moves.  Forward only, unsplit and split."""
+    x, y, _, _ = case(name)
+    B, N, M = x.shape[0], x.shape[1], y.shape[1]
+    nan = float("nan")
+    clean_d2, clean_idx = (a.cpu() for a in nr.nearest_points(x.to(dev), y.to(dev)))
+    assert bool(_lib.last_launch("k_chamfer_nn")[1] & _lib.NR_LAUNCH_SPLIT_X_TO_Y) == (name in SPLIT)
+    # queries: row 0 all NaN, the last row all NaN, row 2 with one NaN coordinate
+    xq = x.clone()
+    xq[:, 0] = nan
+    xq[:, N - 1] = nan
+    xq[:, 2, 1] = nan
+    hit = torch.isnan(xq).any(-1)
+    d2, idx = (a.cpu() for a in nr.nearest_points(xq.to(dev), y.to(dev)))
+    assert int(idx.min()) >= 0 and int(idx.max()) < M
+    assert int(hit.sum()) == 3 * B and bool((idx[hit] == 0).all())
+    assert torch.equal(idx[~hit], clean_idx[~hit]) and torch.equal(d2[~hit], clean_d2[~hit])
+    # targets: the first and last target, the first of the second and third ranges where there are such, and
+    # per item the target that query 1 chose
+    yt = y.clone()
+    dead = torch.zeros((B, M), dtype=torch.bool)
+    dead[:, [0, 7, min(1025, M - 2), min(2050, M - 3), M - 1]] = True
+    dead[torch.arange(B), clean_idx[:, 1].long()] = True
+    yt[dead] = nan
+    d2, idx = (a.cpu() for a in nr.nearest_points(x.to(dev), yt.to(dev)))
+    assert int(idx.min()) >= 0 and int(idx.max()) < M
+    assert not bool(dead.gather(1, idx.long()).any())  # a NaN target is never the nearest
+    kept = ~dead.gather(1, clean_idx.long())
+    assert not bool(kept[:, 1].any()) and bool(kept.any(1).all())
+    assert torch.equal(idx[kept], clean_idx[kept]) and torch.equal(d2[kept], clean_d2[kept])
+    assert bool(torch.isfinite(d2).all()) and bool((d2[~kept] > clean_d2[~kept]).all())
 
 
 def test_non_contiguous_x(dev):
@@ -278,9 +353,18 @@ MESHES = {"ico0": lambda: synthetic.icosphere(0), "ico2": lambda: synthetic.icos
 @pytest.mark.parametrize("mesh", list(MESHES))
 def test_sample_points(dev, mesh, S):
     v, f = MESHES[mesh]()
-    B, F = 3, f.shape[0]
-    vb = torch.as_tensor(jitter(v, B, 0.02, 31).astype(np.float32))
-    u = torch.as_tensor(np.random.RandomState(7).uniform(0, 1, (B, S, 3)).astype(np.float32))
+    vb = torch.as_tensor(jitter(v, 3, 0.02, 31).astype(np.float32))
+    u = torch.as_tensor(np.random.RandomState(7).uniform(0, 1, (3, S, 3)).astype(np.float32))
+    check_sample_points(dev, vb, f, u, 1e-5, "%s S=%d" % (mesh, S))
+
+
+def check_sample_points(dev, vb, f, u, margin, what):
+    """sample_points of the float32 CPU vertices vb [B, V, 3], faces f and u [B, S, 3] against the float64
+    composition: weights, points, the chosen face's cdf bracket, no face of zero area in an item that has
+    area, the vertex gradient, and the composition's own faces wherever u0 * total is further than
+    margin * total from the chosen face's cdf boundaries.  Returns (faces, the float64 composition's faces,
+    whether each sample is outside the margin)."""
+    B, S, F = u.shape[0], u.shape[1], f.shape[0]
     vd = vb.to(dev).requires_grad_(True)
     pts, face, w = nr.sample_points(vd, torch.as_tensor(f, device=dev), S, u=u.to(dev), return_faces=True)
     assert pts.shape == (B, S, 3) and face.shape == (B, S) and face.dtype == torch.int32 and w.shape == (B, S, 3)
@@ -297,7 +381,7 @@ def test_sample_points(dev, mesh, S):
     upper = C.gather(1, face_c)
     lower = torch.where(face_c > 0, C.gather(1, (face_c - 1).clamp(min=0)), torch.zeros_like(upper))
     assert bool((lower - 1e-5 * total <= t).all()) and bool((t <= upper + 1e-5 * total).all())
-    assert bool((area.gather(1, face_c) > 0).all())
+    assert bool(((area.gather(1, face_c) > 0) | (total == 0)).all())
     r = torch.sqrt(u64[..., 1])
     want_w = torch.stack([1 - r, r * (1 - u64[..., 2]), r * u64[..., 2]], -1)
     assert float((w_c - want_w).abs().max()) <= 1e-6
@@ -309,11 +393,80 @@ def test_sample_points(dev, mesh, S):
     for b in range(B):
         for k in range(3):
             want_g[b].index_add_(0, ids[b, :, k], w_c[b, :, k, None] * up[b].double())
-    close_grads(vd.grad, want_g, "%s S=%d vertex grad" % (mesh, S))
+    close_grads(vd.grad, want_g, "%s vertex grad" % what)
     # and the composition itself chooses the same faces wherever u0 is not at a face's boundary
     face_t = nr.sample_points_torch(v64, f, S, u=u64, return_faces=True)[1].long()
-    margin = torch.minimum((t - lower).abs(), (upper - t).abs()) > 1e-5 * total
-    assert torch.equal(face_c[margin], face_t[margin])
+    inside = torch.minimum((t - lower).abs(), (upper - t).abs()) > margin * total
+    assert torch.equal(face_c[inside], face_t[inside])
+    return face_c, face_t, inside
+
+
+MARGIN_CHUNKS = 1e-6  # of the total area; see ico5_dead
+
+
+@functools.lru_cache(maxsize=None)
+def ico5_dead(S):
+    """The icosphere L5 (F 20480: five 4096-face chunks of the scan, all of its 16 waves at work) with faces
+    of zero area (a repeated vertex) at the very start (0, 1: the cdf is 0 before the first live face), on a
+    wave border (255, 256), on a chunk border (4094..4097), every 512th face from 100 on, and at the end
+    (the last three).  B 3, jitter 0.002; the last item has all-zero vertices (no area at all).  u is the
+    file's draw, with the first samples' u0 replaced by 0, 1, the largest float32 below 1, and 0.5.
+
+    A face is 4.9e-5 of the total area wide, so the agreement with the float64 composition's faces is asked
+    outside a margin of 1e-6 of the total, not 1e-5: float32 torch's cdf is within 4.7e-8 of the total of the
+    float64 one (asserted here at 1e-7), u0 * total rounds by 6e-8 relative, and the margin is about ten
+    times their sum.  It excludes 4.5 % of 2000 samples (asserted here at 5 %).
+    Returns float32 CPU vertices [3, V, 3], faces, u [3, S, 3], the dead faces."""
+    v, f = synthetic.icosphere(5)
+    F = f.shape[0]
+    dead = sorted(set([0, 1, 255, 256, 4094, 4095, 4096, 4097] + list(range(100, F, 512)) + [F - 3, F - 2, F - 1]))
+    f = f.copy()
+    f[dead] = f[dead][:, [0, 0, 1]]
+    vb = torch.as_tensor(jitter(v, 3, 0.002, 31).astype(np.float32))
+    vb[2] = 0.
+    u = torch.as_tensor(np.random.RandomState(7).uniform(0, 1, (3, S, 3)).astype(np.float32))
+    special = torch.tensor([0., 1., float(np.nextafter(np.float32(1), np.float32(0))), 0.5])
+    u[:, :min(S, 4), 0] = special[:S]
+    fl = torch.as_tensor(f).long()
+    c32, c64 = point_loss._face_cdf(vb, fl), point_loss._face_cdf(vb.double(), fl)
+    total = c64[:2, -1:]
+    assert float(total.min()) > 0 and float(c64[2].max()) == 0.
+    cdf_err = float(((c32[:2].double() - c64[:2]).abs() / total).max())
+    assert cdf_err <= 1e-7, cdf_err
+    # the dead faces repeat their predecessor's value, the live ones rise
+    rise = torch.diff(c64[:2], dim=1, prepend=torch.zeros(2, 1, dtype=torch.float64)) > 0
+    live = torch.ones(F, dtype=torch.bool)
+    live[dead] = False
+    assert torch.equal(rise, live[None].expand(2, -1))
+    t = (u[:2, :, 0].double() * total).contiguous()
+    edges = torch.cat([torch.zeros(2, 1, dtype=torch.float64), c64[:2]], 1)  # ascending: the nearest edge is a neighbour
+    j = torch.searchsorted(edges, t).clamp(1, F)
+    near = torch.minimum((t - edges.gather(1, j - 1)).abs(), (edges.gather(1, j) - t).abs())
+    excluded = float((near <= MARGIN_CHUNKS * total).double().mean())
+    print("ico5_dead S=%d: cdf error %.3g of the total, %.3g of the samples inside the margin" % (S, cdf_err, excluded))
+    if S >= 1000:
+        assert excluded <= 0.05, excluded
+    return vb, f, u, dead
+
+
+@pytest.mark.parametrize("S", [1, 64, 2000])
+def test_sample_points_across_chunks(dev, S):
+    """A mesh of five scan chunks with zero-area faces on every kind of border, and an item without area
+    beside two that have some: everything test_sample_points asserts, the start of the cdf, and the fallback
+    for u0 * total == total (the last face of positive area, which is not the last face)."""
+    vb, f, u, dead = ico5_dead(S)
+    F = f.shape[0]
+    face, face64, inside = check_sample_points(dev, vb, f, u, MARGIN_CHUNKS, "ico5_dead S=%d" % S)
+    assert not bool(np.isin(face[:2].numpy(), dead).any())
+    assert bool((face[2] == F - 1).all()) and bool((face64[2] == F - 1).all())  # the item without area
+    if S >= 1000:
+        assert float(inside[:2].double().mean()) >= 0.95
+    face32 = nr.sample_points_torch(vb, f, S, u=u, return_faces=True)[1].long()
+    assert F - 4 not in dead and F - 3 in dead
+    for name, got in (("fused", face), ("float64", face64), ("float32", face32)):
+        assert got[:2, 0].tolist() == [2, 2], (name, got[:2, 0])  # u0 = 0: the first face of positive area
+        if S >= 2:
+            assert got[:2, 1].tolist() == [F - 4, F - 4], (name, got[:2, 1])  # u0 = 1: the last one, by the second search
 
 
 def test_sample_points_item_without_area(dev):
