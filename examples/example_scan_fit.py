@@ -1,0 +1,83 @@
+"""Fitting a mesh to a scan: an icosphere's vertices move until its surface passes through a point cloud
+drawn from the teapot, and covers it.
+
+example_chamfer.py's loop with an exact scan -> mesh term.  There both terms go through fresh samples of the
+current mesh, so a scan point between two samples pulls towards the nearest sample, along the surface, and
+the loss carries sampling noise of the order of the sample spacing.  Here
+
+  scan -> mesh   nr.PointMeshLoss(target): the squared distance from every scan point to its closest point
+                 on its closest triangle, with the gradient to that triangle's corners: no sampling, no noise;
+  mesh -> scan   as before: fresh area-weighted samples of the current mesh (nr.sample_points, with the
+                 gradient back to the vertices) and nr.chamfer_distance(..., directions="x_to_y") to the scan,
+                 which keeps the mesh from growing surface where the scan has no points;
+
+plus a small nr.laplacian_loss that keeps the surface smooth, stepped by nr.Adam: every operation of the
+step is a fused HIP kernel.
+
+    python examples/example_scan_fit.py [--iters 300] [--samples 5000] [--level 3] [--out fitted.obj]
+
+The target mesh defaults to tests/data/teapot.obj.
+"""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
+import neural_renderer_v2_pytorch_amd as nr  # noqa: E402
+from neural_renderer_v2_pytorch_amd import synthetic  # noqa: E402
+
+DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests', 'data')
+
+
+class ScanFit(torch.nn.Module):
+    def __init__(self, obj_file, level, samples, smoothness, device, seed=0):
+        super().__init__()
+        self.generator = torch.Generator(device=device).manual_seed(seed)
+        vertices, faces = nr.load_obj(obj_file)
+        target_vertices = torch.as_tensor(vertices).float().to(device)
+        with torch.no_grad():
+            target = nr.sample_points(target_vertices, torch.as_tensor(faces).to(device).int(), samples,
+                                      generator=self.generator)
+        self.scan_to_mesh = nr.PointMeshLoss(target)
+        self.mesh_to_scan = nr.ChamferLoss(target, directions="x_to_y")
+        sphere, sphere_faces = synthetic.icosphere(level, radius=0.5)
+        self.faces = torch.as_tensor(sphere_faces).to(device).int()
+        self.vertices = torch.nn.Parameter(torch.as_tensor(sphere).float().to(device))
+        self.topology = nr.mesh_topology(self.faces, sphere.shape[0])
+        self.samples, self.smoothness = samples, smoothness
+
+    def forward(self):
+        points = nr.sample_points(self.vertices, self.faces, self.samples, generator=self.generator)
+        return (self.scan_to_mesh(self.vertices, self.faces), self.mesh_to_scan(points),
+                nr.laplacian_loss(self.vertices, self.topology))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--obj', default=os.path.join(DATA, 'teapot.obj'))
+    ap.add_argument('--iters', type=int, default=300)
+    ap.add_argument('--samples', type=int, default=5000)
+    ap.add_argument('--level', type=int, default=3, help='icosphere subdivision level')
+    ap.add_argument('--smoothness', type=float, default=0.01, help='weight of the Laplacian loss')
+    ap.add_argument('--gpu', type=int, default=0)
+    ap.add_argument('--out', default=None, help='write the fitted mesh as an .obj file')
+    args = ap.parse_args()
+    model = ScanFit(args.obj, args.level, args.samples, args.smoothness, torch.device('cuda', args.gpu))
+    opt = nr.Adam(model.parameters(), lr=0.01)
+    history = []
+    for _ in range(args.iters):
+        opt.zero_grad()
+        to_mesh, to_scan, laplacian = model()
+        (to_mesh + to_scan + args.smoothness * laplacian).backward()
+        opt.step()
+        history.append((float(to_mesh.detach()), float(to_scan.detach())))
+    print('scan -> mesh: first %.5f, last %.5f; mesh -> scan: first %.5f, last %.5f after %d steps'
+          % (history[0][0], history[-1][0], history[0][1], history[-1][1], len(history)))
+    if args.out:
+        nr.save_obj(args.out, model.vertices.detach().cpu().numpy(), model.faces.cpu().numpy())
+
+
+if __name__ == '__main__':
+    main()

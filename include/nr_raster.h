@@ -551,6 +551,47 @@ NR_API int nr_sample_points_backward(const int32_t* faces, const int32_t* face, 
                                      const float* grad_points, int batch_size, int num_vertices, int num_faces,
                                      int num_samples, float* grad_vertices, void* stream);
 
+/* Point-to-surface distance (point_loss.py point_mesh_distance / closest_points_on_mesh; no reference
+ * counterpart): points [B, N, 3] with the item stride points_batch_stride in elements (0: one [N, 3] set
+ * shared by every item), vertices [B, V, 3] contiguous, faces [F, 3] (trusted: below V).  With T_f the
+ * triangle f as a closed set:
+ *   face[b, i]    = argmin_f dist^2(p_i, T_f), the lowest f among exact float32 ties
+ *   weights[b, i] = the barycentric weights of the closest point of that face over its three corners:
+ *                   c_i = w_0 v[faces[f, 0]] + w_1 v[faces[f, 1]] + w_2 v[faces[f, 2]]
+ *   dist2[b, i]   = |p_i - c_i|^2, the sum of the squared coordinate differences to that closest point
+ *   loss_b        = (1/N) sum_i dist2[b, i]   (one fixed order)
+ * The face is chosen by a float32 distance (the least of the distances to the three edges and, where the
+ * projection falls inside, to the plane); the closest point on the chosen face is then formed in float64
+ * from the float32 inputs, and its weights and squared distance are rounded to float32 once.  Every weight is finite, in [0, 1], and the three
+ * sum to 1 within 1e-6.
+ * A degenerate face (a repeated index, or a float32 cross product (b - a) x (c - a) of exactly zero:
+ * coincident or exactly collinear corners) is the segment between its two most distant corners (the first
+ * of the edges ab, ac, bc among equally long ones), a point when all three coincide (weights 1, 0, 0); the
+ * weight of the unused corner is 0.  Near-degenerate faces get no special promise.
+ * Backward, face and weights held constant (by the envelope theorem the exact gradient of the squared
+ * distance wherever the closest face is unique):
+ *   grad p_i = g_b (2/N) (p_i - c_i)
+ *   grad v_j = -g_b (2/N) sum over (i, k) with faces[face_i, k] == j of w_ik (p_i - c_i)
+ * dist2, face, weights, loss and grad_points are bitwise reproducible (no float atomics, every sum in one
+ * fixed order, the same whether or not the faces were split over several blocks); grad_vertices is
+ * scattered with float atomics and agrees from run to run up to the order of float additions.
+ * Checked before any launch (NR_ERR_ARGS, also for a missing or short workspace): N, F, V >= 1,
+ * B <= 65535, B * N <= INT_MAX - 4096, B * F and 3 B V <= INT_MAX, non-null inputs.  With B == 0 nothing is
+ * launched.  The saved face indices are inside [0, F) whatever the coordinates hold (NaN included). */
+NR_API size_t nr_point_mesh_workspace_bytes(int batch_size, int num_points, int num_faces);
+/* dist2 [B, N], face [B, N], weights [B, N, 3], loss [B]: each may be NULL (not all four); each one given
+ * is fully written. */
+NR_API int nr_point_mesh_forward(const float* points, long long points_batch_stride, const float* vertices,
+                                 const int32_t* faces, int batch_size, int num_points, int num_vertices,
+                                 int num_faces, float* dist2, int32_t* face, float* weights, float* loss,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+/* grad_loss [B] -> grad_points [B, N, 3] (dense, also for shared points), grad_vertices [B, V, 3]
+ * (zero-filled by the call); either may be NULL.  face and weights are the forward's (trusted). */
+NR_API int nr_point_mesh_backward(const float* points, long long points_batch_stride, const float* vertices,
+                                  const int32_t* faces, const int32_t* face, const float* weights,
+                                  const float* grad_loss, int batch_size, int num_points, int num_vertices,
+                                  int num_faces, float* grad_points, float* grad_vertices, void* stream);
+
 /* Diagnostics (no reference counterpart): the kernels replace some IEEE divisions by a shortened
  * form of the compiler's own division sequence inside a guarded operand range (DESIGN.md,
  * "Numerics").  This runs both forms on n operand pairs so tests can check they agree bit for bit. */
@@ -568,7 +609,7 @@ NR_API int nr_profile_enable(int on);
 NR_API int nr_profile_read(const char* kernel, float* ms);
 
 /* Launch record (no reference counterpart; the tests use it to assert which kernel variant ran).
- * For the most recent launch of `kernel` ("k_raster_fwd", "k_raster_bwd" or "k_chamfer_nn": 256 threads) in this process
+ * For the most recent launch of `kernel` ("k_raster_fwd", "k_raster_bwd", or "k_chamfer_nn" / "k_point_face_nn": 256 threads) in this process
  * (process-wide, like the profiling hook; torch issues a backward from its autograd thread): block_threads = threads per block (k_raster_fwd: 256 = four 16x16 quadrants per
  * 32x32 bin, 1024 = one wave per 8x8 block; k_raster_bwd: 256 = 2 pixels per lane, 512 = 1 pixel
  * per lane) and flags = NR_LAUNCH_* bits.  NR_ERR_ARGS when none was recorded. */
@@ -581,7 +622,9 @@ enum { NR_LAUNCH_FUSED_SHADE = 1, NR_LAUNCH_STATIC_CHANNELS = 2, NR_LAUNCH_TWO_P
        /* k_raster_bwd: the feature instantiation (none of the three: the plain path) */
        NR_LAUNCH_LIGHTS = 256, NR_LAUNCH_BACKGROUNDS = 512, NR_LAUNCH_SIL_ONLY = 1024,
        /* k_chamfer_nn: the direction's targets were split over several blocks and combined */
-       NR_LAUNCH_SPLIT_X_TO_Y = 2048, NR_LAUNCH_SPLIT_Y_TO_X = 4096 };
+       NR_LAUNCH_SPLIT_X_TO_Y = 2048, NR_LAUNCH_SPLIT_Y_TO_X = 4096,
+       /* k_point_face_nn: the faces were split over several blocks and combined */
+       NR_LAUNCH_SPLIT_FACES = 8192 };
 NR_API int nr_last_launch(const char* kernel, int* block_threads, int* flags);
 
 #ifdef NR_COUNT_TESTS

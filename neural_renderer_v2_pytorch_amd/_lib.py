@@ -35,6 +35,7 @@ EXPORTS = [
     "nr_attribute_args_size", "nr_attributes_forward", "nr_attributes_backward_workspace_bytes", "nr_attributes_backward",
     "nr_chamfer_workspace_bytes", "nr_chamfer_forward", "nr_chamfer_backward",
     "nr_sample_points_workspace_bytes", "nr_sample_points_forward", "nr_sample_points_backward",
+    "nr_point_mesh_workspace_bytes", "nr_point_mesh_forward", "nr_point_mesh_backward",
 ]
 
 ABI_VERSION = 6  # include/nr_raster.h NR_ABI_VERSION
@@ -43,6 +44,7 @@ NR_LAUNCH_FUSED_SHADE, NR_LAUNCH_STATIC_CHANNELS, NR_LAUNCH_TWO_PX_PER_LANE, NR_
 NR_LAUNCH_HOT_WINDOWS, NR_LAUNCH_DEALT_QUARTERS, NR_LAUNCH_QUADRANTS = 32, 64, 128
 NR_LAUNCH_LIGHTS, NR_LAUNCH_BACKGROUNDS, NR_LAUNCH_SIL_ONLY = 256, 512, 1024  # k_raster_bwd's feature instantiation
 NR_LAUNCH_SPLIT_X_TO_Y, NR_LAUNCH_SPLIT_Y_TO_X = 2048, 4096  # k_chamfer_nn: a direction's targets split over several blocks
+NR_LAUNCH_SPLIT_FACES = 8192  # k_point_face_nn: the faces split over several blocks
 NR_HOT_MAX, NR_HOT_COPIES = 256, 32
 
 c_int, c_float, c_void_p, c_size_t, c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong
@@ -76,6 +78,8 @@ NR_ADAM_MAX_TENSORS, NR_ADAM_CHUNK = 24, 4096  # tensors per launch pair, elemen
 NR_ATTR_MAX_CHANNELS = 64
 NR_CHAMFER_X_TO_Y, NR_CHAMFER_Y_TO_X = 1, 2
 NR_CHAMFER_TILE = 1024  # csrc/nr_point_loss.h PL_TILE: targets staged in LDS at a time
+NR_POINT_MESH_TILE, NR_POINT_MESH_QBLOCK = 256, 1024  # csrc/nr_point_mesh.h PM_TILE (face records in LDS), PM_QBLOCK (queries per block)
+NR_POINT_MESH_SPLIT_BLOCKS = 4096  # PM_SPLIT_BLOCKS: the faces are split over further blocks while a launch has fewer
 
 
 class NrCameraArgs(ctypes.Structure):  # include/nr_raster.h
@@ -130,7 +134,7 @@ def lib():
         raise RuntimeError("neural_renderer_v2_pytorch_amd: HIP library %s is missing; build it with "
                            "__graft_entry__.build() (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_adam_*, nr_attributes_* and point-loss entry points): a library built before them
+    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_adam_*, nr_attributes_*, point-loss and nr_point_mesh_* entry points): a library built before them
     # still reports the version this binding expects
     missing = [name for name in EXPORTS if not hasattr(L, name)]
     if missing:
@@ -206,6 +210,12 @@ def lib():
     L.nr_sample_points_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_size_t, c_void_p]
     L.nr_sample_points_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
+    L.nr_point_mesh_workspace_bytes.restype = c_size_t
+    L.nr_point_mesh_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    L.nr_point_mesh_forward.argtypes = [c_void_p, c_ll, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]
+    L.nr_point_mesh_backward.argtypes = [c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                         c_void_p, c_void_p, c_void_p]
     L.nr_backward_workspace_bytes.restype = c_size_t
     L.nr_backward_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int]
     L.nr_raster_args_size.restype = c_size_t
@@ -225,7 +235,8 @@ def lib():
                         "nr_projection_workspace_bytes", "nr_mesh_loss_workspace_bytes",
                         "nr_image_loss_workspace_bytes", "nr_adam_args_size", "nr_adam_scratch_bytes",
                         "nr_attribute_args_size", "nr_attributes_backward_workspace_bytes",
-                        "nr_chamfer_workspace_bytes", "nr_sample_points_workspace_bytes"):
+                        "nr_chamfer_workspace_bytes", "nr_sample_points_workspace_bytes",
+                        "nr_point_mesh_workspace_bytes"):
             getattr(L, name).restype = c_int
     # a library of another ABI revision (an NR_LIB_PATH override, a stale build) would misread the
     # arguments (e.g. an older nr_rasterize_backward takes its stream where workspace_zeroed is now)
@@ -252,7 +263,7 @@ def lib():
 
 def last_launch(kernel):
     """(threads per block, NR_LAUNCH_* flags) of the latest launch of `kernel` ("k_raster_fwd",
-    "k_raster_bwd" or "k_chamfer_nn") in this process: the variant the library actually ran."""
+    "k_raster_bwd", "k_chamfer_nn" or "k_point_face_nn") in this process: the variant the library actually ran."""
     t, f = c_int(), c_int()
     check(lib().nr_last_launch(kernel.encode(), ctypes.byref(t), ctypes.byref(f)), "nr_last_launch")
     return t.value, f.value

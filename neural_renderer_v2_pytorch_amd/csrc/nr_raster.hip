@@ -27,7 +27,7 @@
 // perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian and
 // flatten regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_adam.h
 // (multi-tensor Adam), nr_attributes.h (per-vertex attribute rendering), nr_point_loss.h (chamfer distance,
-// nearest points and surface sampling), nr_host.h (argument checks); this file holds the extern "C" ABI.
+// nearest points and surface sampling), nr_point_mesh.h (point-to-surface distance), nr_host.h (argument checks); this file holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -59,6 +59,7 @@
 #include "nr_adam.h"
 #include "nr_attributes.h"
 #include "nr_point_loss.h"
+#include "nr_point_mesh.h"
 #include "nr_host.h"
 
 
@@ -1079,6 +1080,108 @@ int nr_sample_points_backward(const int32_t* faces, const int32_t* face, const f
     return check_launch("k_sample_points_bwd");
 }
 
+// ---- point-to-surface distance (nr_point_mesh.h) ----
+// How a launch is cut, as pl_plan cuts a chamfer direction: query blocks per item, and face ranges per
+// query block (the split path) while the launch has fewer than PM_SPLIT_BLOCKS blocks and every range
+// still holds at least a full tile of faces (results do not depend on the cut: nr_point_mesh.h).
+static PlPlan pm_plan(int B, int N, int F) {
+    PlPlan p;
+    p.nqb = (int)(((long long)N + PM_QBLOCK - 1) / PM_QBLOCK);
+    const long long have = (long long)B * p.nqb;
+    const long long want = (PM_SPLIT_BLOCKS + have - 1) / have, most = F / PM_TILE;
+    p.nsplit = (int)(want < most ? want : most);
+    if (p.nsplit < 1) p.nsplit = 1;
+    return p;
+}
+
+static int validate_point_mesh(int B, int N, int V, int F) {
+    if (B < 0) return fail(NR_ERR_ARGS, "bad batch size B=%d", B);
+    if (N <= 0 || F <= 0 || V <= 0) return fail(NR_ERR_ARGS, "empty input N=%d F=%d V=%d (each must be at least 1)", N, F, V);
+    if (B > 65535) return fail(NR_ERR_ARGS, "too many items B=%d (at most 65535)", B);
+    if ((long long)B * N > INT_MAX - 4096 || (long long)B * F > INT_MAX || (long long)B * V > INT_MAX / 3)
+        return fail(NR_ERR_ARGS, "too many points, faces or vertices B=%d N=%d F=%d V=%d", B, N, F, V);
+    return NR_OK;
+}
+
+// records [B, F, PM_REC], the nearest face [B, N], the loop's and the finish's dist2 [B, N] each, and on the
+// split path the partial (d2, f) pairs [B, nsplit, N] twice
+size_t nr_point_mesh_workspace_bytes(int batch_size, int num_points, int num_faces) {
+    if (batch_size <= 0 || num_points <= 0 || num_faces <= 0) return 0;
+    const PlPlan p = pm_plan(batch_size, num_points, num_faces);
+    const size_t bn = align_up((size_t)batch_size * num_points * 4);
+    return align_up((size_t)batch_size * num_faces * PM_REC * 4) + 3 * bn +
+           (p.nsplit > 1 ? 2 * align_up((size_t)batch_size * p.nsplit * num_points * 4) : 0);
+}
+
+int nr_point_mesh_forward(const float* points, long long points_batch_stride, const float* vertices, const int32_t* faces,
+                          int batch_size, int num_points, int num_vertices, int num_faces, float* dist2, int32_t* face,
+                          float* weights, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+    const int B = batch_size, N = num_points, V = num_vertices, F = num_faces;
+    int e = validate_point_mesh(B, N, V, F);
+    if (e) return e;
+    if (points_batch_stride < 0) return fail(NR_ERR_ARGS, "negative points batch stride");
+    if (B == 0) return NR_OK;
+    if (!points || !vertices || !faces) return fail(NR_ERR_ARGS, "null points, vertices or faces");
+    if (!dist2 && !face && !weights && !loss) return fail(NR_ERR_ARGS, "no output asked for");
+    if (!workspace || workspace_bytes < nr_point_mesh_workspace_bytes(B, N, F))
+        return fail(NR_ERR_ARGS, "point_mesh workspace missing or too small");
+    hipStream_t st = (hipStream_t)stream;
+    const PlPlan p = pm_plan(B, N, F);
+    const size_t bn = align_up((size_t)B * N * 4);
+    char* ws = (char*)workspace;
+    float* records = (float*)ws;
+    ws += align_up((size_t)B * F * PM_REC * 4);
+    int32_t* nearest = (int32_t*)ws;
+    float* loop_d2 = (float*)(ws + bn);
+    float* fin_d2 = dist2 ? dist2 : (float*)(ws + 2 * bn);
+    ws += 3 * bn;
+    nr_launch(k_point_face_records, dim3((unsigned)((F + PL_BLOCK - 1) / PL_BLOCK), (unsigned)B), dim3(PL_BLOCK), 0, st, vertices, faces,
+              V, F, records);
+    e = check_launch("k_point_face_records");
+    if (e) return e;
+    PmArgs d;
+    d.points = points, d.p_stride = points_batch_stride, d.records = records, d.N = N, d.F = F, d.nsplit = p.nsplit;
+    if (p.nsplit > 1) {
+        d.dist2 = (float*)ws, d.face = (int32_t*)(ws + align_up((size_t)B * p.nsplit * N * 4));
+    } else {
+        d.dist2 = loop_d2, d.face = nearest;
+    }
+    nr_launch(k_point_face_nn, dim3((unsigned)(p.nqb * p.nsplit), (unsigned)B), dim3(PL_BLOCK), 0, st, d);
+    g_last_point_mesh.store(LaunchRec{PL_BLOCK, p.nsplit > 1 ? NR_LAUNCH_SPLIT_FACES : 0});
+    e = check_launch("k_point_face_nn");
+    if (e) return e;
+    const dim3 per_point((unsigned)((N + PL_BLOCK - 1) / PL_BLOCK), (unsigned)B);
+    if (p.nsplit > 1) {
+        nr_launch(k_chamfer_combine, per_point, dim3(PL_BLOCK), 0, st, (const float*)d.dist2, (const int32_t*)d.face, N, p.nsplit,
+                  loop_d2, nearest);
+        e = check_launch("k_chamfer_combine");
+        if (e) return e;
+    }
+    const bool need_d2 = dist2 || loss;
+    nr_launch(k_point_face_finish, per_point, dim3(PL_BLOCK), 0, st, points, points_batch_stride, vertices, faces,
+              (const int32_t*)nearest, N, V, need_d2 ? fin_d2 : (float*)nullptr, face, weights);
+    e = check_launch("k_point_face_finish");
+    if (e || !loss) return e;
+    nr_launch(k_chamfer_sum, dim3((unsigned)B), dim3(PL_WIDE), 0, st, (const float*)fin_d2, N, (const float*)nullptr, 0, loss);
+    return check_launch("k_chamfer_sum");
+}
+
+int nr_point_mesh_backward(const float* points, long long points_batch_stride, const float* vertices, const int32_t* faces,
+                           const int32_t* face, const float* weights, const float* grad_loss, int batch_size, int num_points,
+                           int num_vertices, int num_faces, float* grad_points, float* grad_vertices, void* stream) {
+    const int B = batch_size, N = num_points, V = num_vertices, F = num_faces;
+    int e = validate_point_mesh(B, N, V, F);
+    if (e) return e;
+    if (points_batch_stride < 0) return fail(NR_ERR_ARGS, "negative points batch stride");
+    if (B == 0 || (!grad_points && !grad_vertices)) return NR_OK;
+    if (!points || !vertices || !faces || !face || !weights || !grad_loss) return fail(NR_ERR_ARGS, "null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    if (grad_vertices && hipMemsetAsync(grad_vertices, 0, (size_t)B * V * 3 * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");
+    nr_launch(k_point_mesh_bwd, dim3((unsigned)((N + PL_BLOCK - 1) / PL_BLOCK), (unsigned)B), dim3(PL_BLOCK), 0, st, points,
+              points_batch_stride, vertices, faces, face, weights, grad_loss, N, V, grad_points, grad_vertices);
+    return check_launch("k_point_mesh_bwd");
+}
+
 // ---- image losses (nr_image_loss.h) ----
 static long long il_chunks(int n) { return ((long long)n + IL_CHUNK - 1) / IL_CHUNK; }
 
@@ -1411,7 +1514,8 @@ int nr_last_launch(const char* kernel, int* block_threads, int* flags) {
     if (!kernel || !block_threads || !flags) return fail(NR_ERR_ARGS, "null argument");
     const LaunchSlot* slot = strcmp(kernel, "k_raster_fwd") == 0 ? &g_last_fwd
                              : strcmp(kernel, "k_raster_bwd") == 0 ? &g_last_bwd
-                             : strcmp(kernel, "k_chamfer_nn") == 0 ? &g_last_chamfer : nullptr;
+                             : strcmp(kernel, "k_chamfer_nn") == 0 ? &g_last_chamfer
+                             : strcmp(kernel, "k_point_face_nn") == 0 ? &g_last_point_mesh : nullptr;
     if (!slot) return fail(NR_ERR_ARGS, "nr_last_launch: unknown kernel name %s", kernel);
     const LaunchRec r = slot->load();
     if (!r.threads) return fail(NR_ERR_ARGS, "nr_last_launch: no %s launch recorded in this process", kernel);

@@ -1,8 +1,9 @@
 """3-D point supervision for the optimisation loop around the renderer: the chamfer distance between two
-point sets, the nearest-neighbour query under it, and area-weighted sampling of points on a mesh.  Each
-is a fused HIP launch sequence (nr_chamfer_* / nr_sample_points_*, include/nr_raster.h) for float32 GPU
-tensors and a torch composition (chamfer_distance_torch / nearest_points_torch / sample_points_torch) for
-every other device and dtype.  The compositions are the tests' reference and the baseline of
+point sets, the nearest-neighbour query under it, area-weighted sampling of points on a mesh, and the
+distance from a point set to the surface of a mesh.  Each is a fused HIP launch sequence (nr_chamfer_* /
+nr_sample_points_* / nr_point_mesh_*, include/nr_raster.h) for float32 GPU tensors and a torch composition
+(chamfer_distance_torch / nearest_points_torch / sample_points_torch / point_mesh_distance_torch /
+closest_points_on_mesh_torch) for every other device and dtype.  The compositions are the tests' reference and the baseline of
 tools/bench_point_loss.py.
 
 Chamfer distance, for x [B, N, 3] and y [B, M, 3] (or one [M, 3] set shared by the items):
@@ -24,6 +25,21 @@ are bitwise identical from run to run.  The sampling backward scatters to the ve
 atomics, as the attribute backward does: its vertex gradient agrees from run to run up to the order of
 float additions.
 
+Point-to-surface distance, for points p [B, N, 3] (or one [N, 3] set shared by the items), vertices
+[B, V, 3] and faces [F, 3], with T_f the triangle f as a closed set:
+
+    loss_b = (1/N) sum_i min_f dist^2(p_i, T_f)
+
+The closest face is the lowest index among exact float32 ties; a degenerate face (a repeated index,
+coincident or exactly collinear corners) is the segment between its two most distant corners, or a
+point.  The fused forward chooses the face with a float32 distance, then forms the closest point on it
+in float64 and saves the face and the barycentric weights; the gradient holds both constant, which by
+the envelope theorem is the exact gradient of the squared distance wherever the closest face is unique.
+Determinism: dist2, face, weights, the loss and the gradient of the points are bitwise reproducible from
+run to run (no float atomics, fixed-order sums, the same whether or not the faces were split over several
+blocks); the gradient of the vertices is scattered with float atomics and agrees up to the order of float
+additions, like the sampling backward.
+
 No call synchronises with the host in the steady state (a faces tensor is range-checked once and
 cached, as everywhere else), so a step can be captured in a HIP graph."""
 import torch
@@ -37,6 +53,8 @@ CHAMFER_TILE = _lib.NR_CHAMFER_TILE  # targets the nearest-neighbour kernel stag
 _DIRECTIONS = {"both": _lib.NR_CHAMFER_X_TO_Y | _lib.NR_CHAMFER_Y_TO_X, "x_to_y": _lib.NR_CHAMFER_X_TO_Y,
                "y_to_x": _lib.NR_CHAMFER_Y_TO_X}
 _CHUNK_ELEMS = 1 << 24  # difference-tensor elements the compositions build at a time
+_CHUNK_PAIRS = 1 << 20  # point-face pairs the point-mesh composition tests at a time (some twenty [pairs, 3] temporaries)
+POINT_MESH_TILE, POINT_MESH_QBLOCK = _lib.NR_POINT_MESH_TILE, _lib.NR_POINT_MESH_QBLOCK  # faces per LDS tile, queries per block
 
 
 def _directions(directions):
@@ -321,6 +339,231 @@ def sample_points(vertices, faces, num_samples, u=None, generator=None, return_f
     v, f, u, single = _prepare_mesh(vertices, faces, num_samples, u, generator)
     points, face, weights = SamplePointsFunction.apply(v.contiguous(), f, u.detach().contiguous())
     return _sample_result(points, face, weights, single, return_faces)
+
+
+# ---- point-to-surface distance ----
+def _prepare_point_mesh(points, vertices, faces):
+    """points as [B, N, 3] or a shared [N, 3], vertices as [B, V, 3], faces as [F, 3] int32 on the vertices'
+    device, and whether the mesh was a single [V, 3] one."""
+    if not torch.is_tensor(points) or points.ndim not in (2, 3) or points.shape[-1] != 3:
+        raise ValueError("points must be a [B, N, 3] or [N, 3] tensor")
+    if not torch.is_tensor(vertices) or vertices.ndim not in (2, 3) or vertices.shape[-1] != 3:
+        raise ValueError("vertices must be a [B, V, 3] or [V, 3] tensor")
+    single = vertices.ndim == 2
+    if single:
+        if points.ndim != 2:
+            raise ValueError("a single [V, 3] mesh takes a single [N, 3] point set, got points of shape %s" % (tuple(points.shape),))
+        vertices = vertices[None]
+    elif points.ndim == 3 and points.shape[0] != vertices.shape[0]:
+        raise ValueError("batch sizes differ: points has %d items, vertices has %d" % (points.shape[0], vertices.shape[0]))
+    f = faces_i32(faces, vertices.device, vertices.shape[1], "faces")
+    if points.shape[-2] == 0 or f.shape[0] == 0:
+        raise ValueError("empty input: N = %d, F = %d (both must be at least 1)" % (points.shape[-2], f.shape[0]))
+    return points, vertices, f, single
+
+
+def _point_triangle(p, a, b, c, degenerate, want_weights):
+    """The closest point of the triangles (a, b, c) to the points p (all [..., 3], broadcast against each
+    other; degenerate [...] bool): the squared distance, and with want_weights the barycentric weights
+    [..., 3] instead.  The rule of csrc/nr_point_mesh.h: a regular face takes the plane's closest point
+    where it falls inside, else the nearest of the edges ab, ac, bc (the first among equals); a degenerate
+    one its longest edge (the first among equals), the third corner's weight 0."""
+    ab, ac, bc, ap, bp = b - a, c - a, c - b, p - a, p - b
+
+    def segment(r, e):
+        ee = (e * e).sum(-1)
+        live = ee > 0
+        t = torch.where(live, (r * e).sum(-1) / torch.where(live, ee, torch.ones_like(ee)), torch.zeros_like(ee)).clamp(0, 1)
+        d = r - t[..., None] * e
+        return (d * d).sum(-1), t
+
+    (e0, t0), (e1, t1), (e2, t2) = segment(ap, ab), segment(ap, ac), segment(bp, bc)
+    d00, d01, d11 = (ab * ab).sum(-1), (ab * ac).sum(-1), (ac * ac).sum(-1)
+    det = d00 * d11 - d01 * d01
+    degenerate = degenerate | ~(det > 0)
+    safe = torch.where(degenerate, torch.ones_like(det), det)
+    d1, d2 = (ap * ab).sum(-1), (ap * ac).sum(-1)
+    v, w = (d11 * d1 - d01 * d2) / safe, (d00 * d2 - d01 * d1) / safe
+    inside = ~degenerate & (v >= 0) & (w >= 0) & (v + w <= 1)
+    if not want_weights:
+        d = ap - v[..., None] * ab - w[..., None] * ac
+        return torch.where(inside, (d * d).sum(-1), torch.minimum(torch.minimum(e0, e1), e2))
+    dbc = (bc * bc).sum(-1)
+    first = torch.where(degenerate, (d00 >= d11) & (d00 >= dbc), (e0 <= e1) & (e0 <= e2))
+    second = torch.where(degenerate, d11 >= dbc, e1 <= e2)
+    zero = torch.zeros_like(t0)
+    on_ab, on_ac, on_bc = torch.stack([1 - t0, t0, zero], -1), torch.stack([1 - t1, zero, t1], -1), torch.stack([zero, 1 - t2, t2], -1)
+    edge = torch.where(first[..., None], on_ab, torch.where(second[..., None], on_ac, on_bc))
+    return torch.where(inside[..., None], torch.stack([(1 - v - w).clamp(min=0), v, w], -1), edge)
+
+
+def _mesh_corners(v, fl):
+    """The corners [B, F, 3, 3] of the faces fl (int64) and which faces are degenerate [B, F]: a repeated index
+    or an exactly zero cross product of the edges ab and ac."""
+    tri = v[:, fl]
+    n = torch.linalg.cross(tri[:, :, 1] - tri[:, :, 0], tri[:, :, 2] - tri[:, :, 0], dim=-1)
+    repeated = (fl[:, 0] == fl[:, 1]) | (fl[:, 0] == fl[:, 2]) | (fl[:, 1] == fl[:, 2])
+    return tri, repeated[None] | (n == 0).all(-1)
+
+
+def _nearest_face_torch(p, tri, degenerate):
+    """int64 [B, N]: the nearest face of every point of p [B, N, 3] (torch.min: the first of equal minima),
+    chunked over N."""
+    B, N, F = p.shape[0], p.shape[1], tri.shape[1]
+    step = max(1, _CHUNK_PAIRS // (F * B))
+    a, b, c, deg = tri[:, None, :, 0], tri[:, None, :, 1], tri[:, None, :, 2], degenerate[:, None]
+    return torch.cat([_point_triangle(p[:, i:i + step, None, :], a, b, c, deg, False).min(dim=2)[1] for i in range(0, N, step)], 1)
+
+
+def _closest_torch(p, v, fl, face):
+    """(dist2 [B, N], int64 face [B, N], weights [B, N, 3]) of p [B, N, 3] against the mesh; dist2 is
+    differentiable in p and v, face (its own arg-min when None) and weights are constants."""
+    with torch.no_grad():
+        tri, degenerate = _mesh_corners(v, fl)
+        if face is None:
+            face = _nearest_face_torch(p, tri, degenerate)
+        own = tri.gather(1, face[..., None, None].expand(-1, -1, 3, 3))
+        weights = _point_triangle(p, own[:, :, 0], own[:, :, 1], own[:, :, 2], degenerate.gather(1, face), True)
+    corners = fl[face]  # [B, N, 3]
+    c = sum(weights[..., k, None] * v.gather(1, corners[..., k, None].expand(-1, -1, 3)) for k in range(3))
+    d = p - c
+    return (d * d).sum(-1), face, weights
+
+
+def _expanded(points, B):
+    return points if points.ndim == 3 else points[None].expand(B, -1, -1)
+
+
+def closest_points_on_mesh_torch(points, vertices, faces):
+    """closest_points_on_mesh as torch ops; any device and floating dtype (dist2 and weights in that dtype)."""
+    p, v, f, single = _prepare_point_mesh(points, vertices, faces)
+    with torch.no_grad():
+        dist2, face, weights = _closest_torch(_expanded(p, v.shape[0]), v, f.long(), None)
+    face = face.to(torch.int32)
+    return (dist2[0], face[0], weights[0]) if single else (dist2, face, weights)
+
+
+def point_mesh_distance_torch(points, vertices, faces, average=False, face=None):
+    """point_mesh_distance as torch ops: the nearest face from a chunked [B, n, F] point-triangle test (held
+    constant, as are the weights of the closest point), then a gather and a mean; any device and floating
+    dtype.  With face [B, N] (or [N] for single inputs) given, that assignment replaces the arg-min: the
+    closest point on the given face is still computed, differentiably."""
+    p, v, f, single = _prepare_point_mesh(points, vertices, faces)
+    B = v.shape[0]
+    pb = _expanded(p, B)
+    if face is not None:
+        face = torch.as_tensor(face, device=v.device).long().reshape(B, pb.shape[1])
+        if face.numel() and (int(face.min()) < 0 or int(face.max()) >= f.shape[0]):
+            raise IndexError("face index out of range [0, %d)" % f.shape[0])
+    dist2 = _closest_torch(pb, v, f.long(), face)[0]
+    return _finish(dist2.mean(1), single, average)
+
+
+def _points_stride(p):
+    return 0 if p.ndim == 2 or p.stride(0) == 0 else p.shape[1] * 3
+
+
+def _point_mesh_launch(p, v, f, want_loss):
+    """p as _dense_y gives it, v [B, V, 3] contiguous, f [F, 3] int32 -> (loss or None, dist2, face, weights)."""
+    B, N, V, F = v.shape[0], p.shape[-2], v.shape[1], f.shape[0]
+    dev = v.device
+    L = _lib.lib()
+    dist2 = torch.empty((B, N), dtype=torch.float32, device=dev)
+    face = torch.empty((B, N), dtype=torch.int32, device=dev)
+    weights = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    loss = torch.empty(B, dtype=torch.float32, device=dev) if want_loss else None
+    ws = torch.empty(L.nr_point_mesh_workspace_bytes(B, N, F), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(L.nr_point_mesh_forward(_lib.ptr(p), _points_stride(p), _lib.ptr(v), _lib.ptr(f), B, N, V, F, _lib.ptr(dist2),
+                                           _lib.ptr(face), _lib.ptr(weights), _lib.ptr(loss), _lib.ptr(ws), ws.numel(),
+                                           _lib.stream_of(v)), "nr_point_mesh_forward")
+    return loss, dist2, face, weights
+
+
+class PointMeshFunction(torch.autograd.Function):
+    """points as _dense_y gives them, vertices [B, V, 3] float32 contiguous on the GPU, faces [F, 3] int32 ->
+    loss [B]; saves the chosen faces and the weights (and the inputs, which the backward reads again)."""
+
+    @staticmethod
+    def forward(ctx, points, vertices, faces):
+        loss, _, face, weights = _point_mesh_launch(points, vertices, faces, True)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ctx.save_for_backward(points, vertices, faces, face, weights)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        need_p, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_p or need_v):
+            return None, None, None
+        p, v, f, face, weights = ctx.saved_tensors
+        B, N, V = v.shape[0], p.shape[-2], v.shape[1]
+        if need_p and p.ndim == 2:
+            raise RuntimeError("shared points that take a gradient must be passed batch-expanded")
+        g = grad_loss.to(torch.float32).contiguous()
+        gp = torch.empty((B, N, 3), dtype=torch.float32, device=v.device) if need_p else None
+        gv = torch.empty_like(v) if need_v else None
+        with _lib.on_device(v.device):
+            _lib.check(_lib.lib().nr_point_mesh_backward(_lib.ptr(p), _points_stride(p), _lib.ptr(v), _lib.ptr(f), _lib.ptr(face),
+                                                         _lib.ptr(weights), _lib.ptr(g), B, N, V, f.shape[0], _lib.ptr(gp),
+                                                         _lib.ptr(gv), _lib.stream_of(v)), "nr_point_mesh_backward")
+        return gp, gv, None
+
+
+def point_mesh_distance(points, vertices, faces, average=False):
+    """(1/N) sum_i min_f dist^2(p_i, T_f) per item, T_f the triangle f as a closed set: the mean squared
+    distance from the points to the surface.  [B] for vertices [B, V, 3], a 0-dim tensor for [V, 3] or with
+    average=True (the mean over the items).  points is [B, N, 3], or [N, 3]: alone with a single mesh, shared
+    by the items of a batched one (read in place; expanded only when it takes a gradient, so that torch's
+    expand backward sums the items).  faces is [F, 3], shared (out-of-range indices raise IndexError).
+    N = 0, F = 0 and differing batch sizes raise ValueError; the inputs are taken to be finite.
+
+    The lowest face index wins among exact float32 ties.  A degenerate face (a repeated index, coincident
+    or exactly collinear corners) counts as the segment between its two most distant corners, or a point.
+    The gradient holds the face choice and the barycentric weights w of the closest point c_i constant:
+    p_i takes g_b (2/N) (p_i - c_i), vertex j takes -g_b (2/N) sum w_ik (p_i - c_i) over the corners (i, k) that
+    are j.  By the envelope theorem this is the exact gradient of the squared distance wherever the
+    closest face is unique.  float32 GPU tensors run the fused kernels (nr_point_mesh_*); everything else
+    point_mesh_distance_torch."""
+    if not _fused(points, vertices):
+        return point_mesh_distance_torch(points, vertices, faces, average)
+    p, v, f, single = _prepare_point_mesh(points, vertices, faces)
+    if p.ndim == 2 and p.requires_grad and torch.is_grad_enabled():
+        p = p[None].expand(v.shape[0], -1, -1)
+    return _finish(PointMeshFunction.apply(_dense_y(p), v.contiguous(), f), single, average)
+
+
+def closest_points_on_mesh(points, vertices, faces):
+    """For every point of points ([B, N, 3], or [N, 3] alone or shared) its closest point on the mesh:
+    (dist2 [B, N] float32, face [B, N] int32: the closest face, the lowest index among exact ties,
+    weights [B, N, 3] float32: the barycentric weights of the closest point over that face's corners, so
+    that it is sum_k weights[..., k] * vertices[faces[face, k]]).  dist2 is the squared distance to exactly
+    that point.  All three are detached; for a custom loss rebuild the closest point from face and weights
+    in torch and let the gradient follow torch's own gather."""
+    if not _fused(points, vertices):
+        return closest_points_on_mesh_torch(points, vertices, faces)
+    p, v, f, single = _prepare_point_mesh(points, vertices, faces)
+    with torch.no_grad():
+        _, dist2, face, weights = _point_mesh_launch(_dense_y(p.detach()), v.detach().contiguous(), f, False)
+    return (dist2[0], face[0], weights[0]) if single else (dist2, face, weights)
+
+
+class PointMeshLoss(torch.nn.Module):
+    """point_mesh_distance from an optional fixed point set held by the module (a buffer: it moves with
+    .to()) to the mesh given to forward; forward(vertices, faces) uses it, forward(vertices, faces, points)
+    the given points."""
+
+    def __init__(self, points=None, average=False):
+        super().__init__()
+        self.register_buffer("points", None if points is None else torch.as_tensor(points).detach().clone())
+        self.average = average
+
+    def forward(self, vertices, faces, points=None):
+        points = self.points if points is None else points
+        if points is None:
+            raise ValueError("PointMeshLoss needs points: pass them, or construct the module with a point set")
+        return point_mesh_distance(points, vertices, faces, self.average)
 
 
 class ChamferLoss(torch.nn.Module):
