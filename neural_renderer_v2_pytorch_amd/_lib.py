@@ -17,27 +17,6 @@ NR_DRAW_RGB = 1
 NR_DRAW_SILHOUETTES = 2
 NR_DRAW_DEPTH = 4
 
-# every symbol declared in include/nr_raster.h
-EXPORTS = [
-    "nr_last_error", "nr_version", "nr_workspace_bytes", "nr_face_index_map_forward_safe",
-    "nr_compute_weight_map", "nr_mask_foreground_forward", "nr_mask_foreground_backward",
-    "nr_differentiation_backward", "nr_num_channels", "nr_rasterize_forward", "nr_rasterize_backward",
-    "nr_backward_workspace_bytes", "nr_profile_enable", "nr_profile_read",
-    "nr_selftest_division", "nr_halo_bytes", "nr_raster_args_size", "nr_rasterize_backward_params",
-    "nr_camera_forward", "nr_camera_backward", "nr_camera_workspace_bytes", "nr_texture_packed_bytes",
-    "nr_last_launch", "nr_hot_acc_bytes",
-    "nr_projection_args_size", "nr_projection_forward", "nr_projection_workspace_bytes", "nr_projection_backward",
-    "nr_mesh_loss_workspace_bytes", "nr_laplacian_forward", "nr_laplacian_backward", "nr_flatten_forward",
-    "nr_flatten_backward",
-    "nr_image_loss_workspace_bytes", "nr_pointwise_loss_forward", "nr_pointwise_loss_backward", "nr_iou_loss_forward",
-    "nr_iou_loss_backward",
-    "nr_adam_args_size", "nr_adam_scratch_bytes", "nr_adam_step",
-    "nr_attribute_args_size", "nr_attributes_forward", "nr_attributes_backward_workspace_bytes", "nr_attributes_backward",
-    "nr_chamfer_workspace_bytes", "nr_chamfer_forward", "nr_chamfer_backward",
-    "nr_sample_points_workspace_bytes", "nr_sample_points_forward", "nr_sample_points_backward",
-    "nr_point_mesh_workspace_bytes", "nr_point_mesh_forward", "nr_point_mesh_backward",
-]
-
 ABI_VERSION = 6  # include/nr_raster.h NR_ABI_VERSION
 
 NR_LAUNCH_FUSED_SHADE, NR_LAUNCH_STATIC_CHANNELS, NR_LAUNCH_TWO_PX_PER_LANE, NR_LAUNCH_DEEP_FIRST, NR_LAUNCH_SPLIT = 1, 2, 4, 8, 16
@@ -123,6 +102,73 @@ class NrAttributeArgs(ctypes.Structure):  # include/nr_raster.h
     ]
 
 
+_P, _args = c_void_p, ctypes.POINTER
+_pointwise = [_P, c_ll, _P, c_ll, _P, c_ll, c_int, c_int, c_float, c_int, c_int]
+
+# every symbol declared in include/nr_raster.h: name -> (restype, argtypes)
+SIGNATURES = {
+    "nr_last_error": (ctypes.c_char_p, []),
+    "nr_version": (c_int, []),
+    "nr_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "nr_face_index_map_forward_safe": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_float, c_int, c_float, c_float, _P,
+                                               c_size_t, _P]),
+    "nr_compute_weight_map": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
+    "nr_mask_foreground_forward": (c_int, [_P, _P, _P, c_ll, c_int, _P]),
+    "nr_mask_foreground_backward": (c_int, [_P, _P, _P, c_ll, c_int, _P]),
+    "nr_differentiation_backward": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "nr_num_channels": (c_int, [c_int]),
+    "nr_rasterize_forward": (c_int, [_args(NrRasterArgs), _P, _P]),
+    "nr_rasterize_backward": (c_int, [_args(NrRasterArgs), _P, _P, _P, _P, c_size_t, c_int, _P]),
+    "nr_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "nr_profile_enable": (c_int, [c_int]),
+    "nr_profile_read": (c_int, [ctypes.c_char_p, ctypes.POINTER(c_float)]),
+    "nr_selftest_division": (c_int, [_P, _P, _P, _P, c_ll, _P]),
+    "nr_halo_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "nr_raster_args_size": (c_size_t, []),
+    "nr_rasterize_backward_params": (c_int, [_args(NrRasterArgs), _P, _P, _P, _P]),
+    "nr_camera_forward": (c_int, [_args(NrCameraArgs), _P, _P]),
+    "nr_camera_backward": (c_int, [_args(NrCameraArgs), _P, _P, _P, _P, c_size_t, _P]),
+    "nr_camera_workspace_bytes": (c_size_t, [c_int]),
+    "nr_texture_packed_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "nr_last_launch": (c_int, [ctypes.c_char_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "nr_hot_acc_bytes": (c_size_t, [c_int]),
+    "nr_projection_args_size": (c_size_t, []),
+    "nr_projection_forward": (c_int, [_args(NrProjectionArgs), _P, _P]),
+    "nr_projection_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "nr_projection_backward": (c_int, [_args(NrProjectionArgs), _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "nr_mesh_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "nr_laplacian_forward": (c_int, [_P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "nr_laplacian_backward": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P]),
+    "nr_flatten_forward": (c_int, [_P, _P, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),
+    "nr_flatten_backward": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
+    "nr_image_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "nr_pointwise_loss_forward": (c_int, _pointwise + [_P, _P, c_size_t, _P]),
+    "nr_pointwise_loss_backward": (c_int, _pointwise + [_P, _P, _P]),
+    "nr_iou_loss_forward": (c_int, [_P, c_ll, _P, c_ll, c_float, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "nr_iou_loss_backward": (c_int, [_P, c_ll, _P, c_float, c_int, c_int, _P, _P, _P]),
+    "nr_adam_args_size": (c_size_t, []),
+    "nr_adam_scratch_bytes": (c_size_t, [c_int]),
+    "nr_adam_step": (c_int, [_args(NrAdamArgs), _P]),
+    "nr_attribute_args_size": (c_size_t, []),
+    "nr_attributes_forward": (c_int, [_args(NrAttributeArgs), _P, _P]),
+    "nr_attributes_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "nr_attributes_backward": (c_int, [_args(NrAttributeArgs), _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "nr_chamfer_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "nr_chamfer_forward": (c_int, [_P, _P, c_ll, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "nr_chamfer_backward": (c_int, [_P, _P, c_ll, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "nr_sample_points_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "nr_sample_points_forward": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "nr_sample_points_backward": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "nr_point_mesh_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "nr_point_mesh_forward": (c_int, [_P, c_ll, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "nr_point_mesh_backward": (c_int, [_P, c_ll, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
+}
+EXPORTS = list(SIGNATURES)
+
+# the library's sizeof of each argument struct against its ctypes mirror
+STRUCT_SIZES = [("nr_projection_args_size", NrProjectionArgs), ("nr_adam_args_size", NrAdamArgs),
+                ("nr_attribute_args_size", NrAttributeArgs), ("nr_raster_args_size", NrRasterArgs)]
+
 _lib = None
 
 
@@ -140,123 +186,19 @@ def lib():
     if missing:
         raise RuntimeError("neural_renderer_v2_pytorch_amd: %s lacks %s; this binding needs a newer build of the "
                            "library (rebuild with __graft_entry__.build())" % (LIB_PATH, ", ".join(missing)))
-    L.nr_last_error.restype = ctypes.c_char_p
-    L.nr_last_error.argtypes = []
-    L.nr_version.restype = c_int
-    L.nr_workspace_bytes.restype = c_size_t
-    L.nr_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.nr_num_channels.restype = c_int
-    L.nr_num_channels.argtypes = [c_int]
-    L.nr_face_index_map_forward_safe.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int,
-                                                 c_float, c_float, c_void_p, c_size_t, c_void_p]
-    L.nr_compute_weight_map.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
-    L.nr_mask_foreground_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p]
-    L.nr_mask_foreground_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_ll, c_int, c_void_p]
-    L.nr_differentiation_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]
-    L.nr_rasterize_forward.argtypes = [ctypes.POINTER(NrRasterArgs), c_void_p, c_void_p]
-    L.nr_rasterize_backward.argtypes = [ctypes.POINTER(NrRasterArgs), c_void_p, c_void_p, c_void_p, c_void_p,
-                                        c_size_t, c_int, c_void_p]
-    L.nr_rasterize_backward_params.argtypes = [ctypes.POINTER(NrRasterArgs), c_void_p, c_void_p, c_void_p, c_void_p]
-    L.nr_camera_forward.argtypes = [ctypes.POINTER(NrCameraArgs), c_void_p, c_void_p]
-    L.nr_camera_backward.argtypes = [ctypes.POINTER(NrCameraArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
-                                     c_void_p]
-    L.nr_texture_packed_bytes.restype = c_size_t
-    L.nr_texture_packed_bytes.argtypes = [c_int, c_int, c_int]
-    L.nr_camera_workspace_bytes.restype = c_size_t
-    L.nr_camera_workspace_bytes.argtypes = [c_int]
-    L.nr_projection_args_size.restype = c_size_t
-    L.nr_projection_args_size.argtypes = []
-    L.nr_projection_workspace_bytes.restype = c_size_t
-    L.nr_projection_workspace_bytes.argtypes = [c_int, c_int]
-    L.nr_projection_forward.argtypes = [ctypes.POINTER(NrProjectionArgs), c_void_p, c_void_p]
-    L.nr_projection_backward.argtypes = [ctypes.POINTER(NrProjectionArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_size_t, c_void_p]
-    L.nr_mesh_loss_workspace_bytes.restype = c_size_t
-    L.nr_mesh_loss_workspace_bytes.argtypes = [c_int, c_int]
-    L.nr_laplacian_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
-                                       c_void_p]
-    L.nr_laplacian_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]
-    L.nr_flatten_forward.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
-                                     c_void_p]
-    L.nr_flatten_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]
-    L.nr_image_loss_workspace_bytes.restype = c_size_t
-    L.nr_image_loss_workspace_bytes.argtypes = [c_int, c_int]
-    pointwise = [c_void_p, c_ll, c_void_p, c_ll, c_void_p, c_ll, c_int, c_int, c_float, c_int, c_int]
-    L.nr_pointwise_loss_forward.argtypes = pointwise + [c_void_p, c_void_p, c_size_t, c_void_p]
-    L.nr_pointwise_loss_backward.argtypes = pointwise + [c_void_p, c_void_p, c_void_p]
-    L.nr_iou_loss_forward.argtypes = [c_void_p, c_ll, c_void_p, c_ll, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                      c_size_t, c_void_p]
-    L.nr_iou_loss_backward.argtypes = [c_void_p, c_ll, c_void_p, c_float, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    L.nr_adam_args_size.restype = c_size_t
-    L.nr_adam_args_size.argtypes = []
-    L.nr_adam_scratch_bytes.restype = c_size_t
-    L.nr_adam_scratch_bytes.argtypes = [c_int]
-    L.nr_adam_step.argtypes = [ctypes.POINTER(NrAdamArgs), c_void_p]
-    L.nr_attribute_args_size.restype = c_size_t
-    L.nr_attribute_args_size.argtypes = []
-    L.nr_attributes_forward.argtypes = [ctypes.POINTER(NrAttributeArgs), c_void_p, c_void_p]
-    L.nr_attributes_backward_workspace_bytes.restype = c_size_t
-    L.nr_attributes_backward_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.nr_attributes_backward.argtypes = [ctypes.POINTER(NrAttributeArgs), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]
-    L.nr_chamfer_workspace_bytes.restype = c_size_t
-    L.nr_chamfer_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    L.nr_chamfer_forward.argtypes = [c_void_p, c_void_p, c_ll, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
-                                     c_void_p, c_void_p, c_size_t, c_void_p]
-    L.nr_chamfer_backward.argtypes = [c_void_p, c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
-                                      c_void_p, c_void_p]
-    L.nr_sample_points_workspace_bytes.restype = c_size_t
-    L.nr_sample_points_workspace_bytes.argtypes = [c_int, c_int]
-    L.nr_sample_points_forward.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                           c_void_p, c_size_t, c_void_p]
-    L.nr_sample_points_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
-    L.nr_point_mesh_workspace_bytes.restype = c_size_t
-    L.nr_point_mesh_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.nr_point_mesh_forward.argtypes = [c_void_p, c_ll, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
-                                        c_void_p, c_void_p, c_size_t, c_void_p]
-    L.nr_point_mesh_backward.argtypes = [c_void_p, c_ll, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
-                                         c_void_p, c_void_p, c_void_p]
-    L.nr_backward_workspace_bytes.restype = c_size_t
-    L.nr_backward_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int]
-    L.nr_raster_args_size.restype = c_size_t
-    L.nr_raster_args_size.argtypes = []
-    L.nr_hot_acc_bytes.restype = c_size_t
-    L.nr_hot_acc_bytes.argtypes = [c_int]
-    L.nr_halo_bytes.restype = c_size_t
-    L.nr_halo_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    L.nr_selftest_division.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_ll, c_void_p]
-    L.nr_last_launch.argtypes = [ctypes.c_char_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
-    L.nr_profile_enable.argtypes = [c_int]
-    L.nr_profile_read.argtypes = [ctypes.c_char_p, ctypes.POINTER(c_float)]
-    for name in EXPORTS:
-        if name not in ("nr_last_error", "nr_workspace_bytes", "nr_num_channels", "nr_backward_workspace_bytes",
-                        "nr_halo_bytes", "nr_raster_args_size", "nr_camera_workspace_bytes",
-                        "nr_texture_packed_bytes", "nr_hot_acc_bytes", "nr_projection_args_size",
-                        "nr_projection_workspace_bytes", "nr_mesh_loss_workspace_bytes",
-                        "nr_image_loss_workspace_bytes", "nr_adam_args_size", "nr_adam_scratch_bytes",
-                        "nr_attribute_args_size", "nr_attributes_backward_workspace_bytes",
-                        "nr_chamfer_workspace_bytes", "nr_sample_points_workspace_bytes",
-                        "nr_point_mesh_workspace_bytes"):
-            getattr(L, name).restype = c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     # a library of another ABI revision (an NR_LIB_PATH override, a stale build) would misread the
     # arguments (e.g. an older nr_rasterize_backward takes its stream where workspace_zeroed is now)
-    if L.nr_projection_args_size() != ctypes.sizeof(NrProjectionArgs):
-        raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has a %d-byte NrProjectionArgs; this binding needs %d "
-                           "bytes (rebuild with __graft_entry__.build())"
-                           % (LIB_PATH, L.nr_projection_args_size(), ctypes.sizeof(NrProjectionArgs)))
-    if L.nr_adam_args_size() != ctypes.sizeof(NrAdamArgs):
-        raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has a %d-byte NrAdamArgs; this binding needs %d bytes "
-                           "(rebuild with __graft_entry__.build())"
-                           % (LIB_PATH, L.nr_adam_args_size(), ctypes.sizeof(NrAdamArgs)))
-    if L.nr_attribute_args_size() != ctypes.sizeof(NrAttributeArgs):
-        raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has a %d-byte NrAttributeArgs; this binding needs %d "
-                           "bytes (rebuild with __graft_entry__.build())"
-                           % (LIB_PATH, L.nr_attribute_args_size(), ctypes.sizeof(NrAttributeArgs)))
-    if L.nr_version() != ABI_VERSION or L.nr_raster_args_size() != ctypes.sizeof(NrRasterArgs):
-        raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has ABI version %d with a %d-byte NrRasterArgs; this "
-                           "binding needs version %d and %d bytes (rebuild with __graft_entry__.build())"
-                           % (LIB_PATH, L.nr_version(), L.nr_raster_args_size(), ABI_VERSION,
-                              ctypes.sizeof(NrRasterArgs)))
+    for size_fn, struct in STRUCT_SIZES:
+        if getattr(L, size_fn)() != ctypes.sizeof(struct):
+            raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has a %d-byte %s; this binding needs %d bytes "
+                               "(rebuild with __graft_entry__.build())"
+                               % (LIB_PATH, getattr(L, size_fn)(), struct.__name__, ctypes.sizeof(struct)))
+    if L.nr_version() != ABI_VERSION:
+        raise RuntimeError("neural_renderer_v2_pytorch_amd: %s has ABI version %d; this binding needs version %d "
+                           "(rebuild with __graft_entry__.build())" % (LIB_PATH, L.nr_version(), ABI_VERSION))
     _lib = L
     return L
 

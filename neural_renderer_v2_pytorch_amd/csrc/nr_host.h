@@ -1,4 +1,4 @@
-// nr_host.h -- host-side argument validation and Shade construction
+// nr_host.h -- host-side helpers: launch grids, workspace layouts, split plan, argument validation and Shade construction
 // Part of nr_raster.hip (one translation unit); see that file and DESIGN.md.
 #pragma once
 
@@ -6,12 +6,121 @@
 
 namespace {
 
+// the raster the kernels work on: twice the output's side with anti-aliasing
+int internal_size(int anti_aliasing, int image_size) { return anti_aliasing ? 2 * image_size : image_size; }
+
+// texels of one packed RGBA texture (textures_packed, the backward's g4): H * W rounded up to four
+size_t packed_texels(int H, int W) { return ((size_t)H * W + 3) & ~size_t(3); }
+
+// one thread per element: blocks of `block` threads over n elements, by `items` in y
+dim3 grid_1d(long long n, int block, int items = 1) { return dim3((unsigned)((n + block - 1) / block), (unsigned)items); }
+
+// hipMemsetAsync to zero; on failure *e takes the status the entry point returns
+bool zero_async(void* p, size_t bytes, hipStream_t st, int* e) {
+    if (hipMemsetAsync(p, 0, bytes, st) == hipSuccess) return true;
+    *e = check_launch("hipMemsetAsync");
+    return false;
+}
+
+// ---- workspace layouts ----
+// A workspace is cut once: every piece starts where the one before it ended, rounded up to 256 bytes.
+// Each *_layout below lists its pieces' byte offsets in order, then the total (a braced list is evaluated
+// left to right); the nr_*_bytes functions return that total, and the entry points test the caller's size
+// against it and point into the buffer by the offsets.
+struct Cutter {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t at = off;
+        off += align_up(bytes);
+        return at;
+    }
+    size_t take_if(bool wanted, size_t bytes) { return wanted ? take(bytes) : off; }
+};
+
+// forward: [bbox int2 B*F][mask u32 B*nbins*nwords][per-face-group bin candidate counts u8
+// B*groups*nbins][bin order i32 B*nbins][split counts: one i32 per list, at most 8 lists] (the last three:
+// deep-bin dispatch order, run_face_index; groups = the setup's face groups of SETUP_FACES)
+struct FwdLayout {
+    size_t bbox, mask, part, order, split_cnt, total;
+};
+FwdLayout forward_layout(int B, int F, const Geom& g) {
+    Cutter c;
+    return {c.take((size_t)B * F * sizeof(int2)), c.take((size_t)B * g.nbins * g.nwords * 4),
+            c.take((size_t)B * setup_groups(g) * g.nbins), c.take((size_t)B * g.nbins * 4), c.take(8 * sizeof(int)), c.off};
+}
+
+// backward: [gF: B F 9 face-corner floats][g4: Bt HWp RGBA texel rows][lights: gN: B F 9][gU: B V 3];
+// the first zero_bytes start at zero (one memset, or the forward's setup zeroed them:
+// NrRasterArgs.bwd_workspace): everything before gU, which k_vnormal_bwd writes in full
+struct BwdLayout {
+    size_t gF, g4, gN, zero_bytes, gU, total;
+};
+BwdLayout backward_layout(int B, int F, int V, int tex_items, int tex_height, int tex_width, bool lit) {
+    Cutter c;
+    return {c.take((size_t)B * F * 9 * 4), c.take_if(tex_items > 0, (size_t)tex_items * packed_texels(tex_height, tex_width) * 16),
+            c.take_if(lit, (size_t)B * F * 9 * 4), c.off, c.take_if(lit, (size_t)B * V * 3 * 4), c.off};
+}
+
+// halo cache (nr_shade.h): the B items' halo values, then one byte per (item, 32x32 bin), nonzero when the
+// bin has a foreground pixel (written by the forward, read by the backward to skip background tiles)
+struct HaloLayout {
+    size_t flags, total;
+};
+HaloLayout halo_layout(int B, int S, int C) {
+    const size_t flags = (size_t)((long long)B * halo_item_floats(S, C) * 4);
+    return {flags, flags + (((size_t)B * make_geom(0, S).nbins + 3) & ~size_t(3))};
+}
+
+// How a nearest-neighbour launch (a chamfer direction: PL_*, point-to-surface: PM_*) is cut: query blocks per
+// item, and target ranges per query block (more than one -- the split path -- while the launch has fewer
+// than split_blocks blocks and every range still holds at least a full tile of targets: few queries against
+// many targets would otherwise leave most of the chip idle).  Results do not depend on the cut.
+struct SplitPlan {
+    int nqb, nsplit;
+};
+SplitPlan split_plan(int B, int nq, int nt, int qblock, int tile, int split_blocks) {
+    SplitPlan p;
+    p.nqb = (int)(((long long)nq + qblock - 1) / qblock);
+    const long long have = (long long)B * p.nqb;
+    const long long want = (split_blocks + have - 1) / have, most = nt / tile;
+    p.nsplit = (int)(want < most ? want : most);
+    if (p.nsplit < 1) p.nsplit = 1;
+    return p;
+}
+
+// one chamfer direction: the per-query minima [B, nq] and, on the split path, the partial d2 and j
+// [B, nsplit, nq] each
+struct ChamferLayout {
+    SplitPlan plan;
+    size_t minima, part_d2, part_j, total;
+};
+ChamferLayout chamfer_layout(int B, int nq, int nt) {
+    const SplitPlan p = split_plan(B, nq, nt, PL_QBLOCK, PL_TILE, PL_SPLIT_BLOCKS);
+    const size_t part = (size_t)B * p.nsplit * nq * 4;
+    Cutter c;
+    return {p, c.take((size_t)B * nq * 4), c.take_if(p.nsplit > 1, part), c.take_if(p.nsplit > 1, part), c.off};
+}
+
+// point-to-surface: records [B, F, PM_REC], the nearest face [B, N], the loop's and the finish's dist2 [B, N]
+// each, and on the split path the partial d2 and f [B, nsplit, N] each
+struct PointMeshLayout {
+    SplitPlan plan;
+    size_t records, nearest, loop_d2, fin_d2, part_d2, part_f, total;
+};
+PointMeshLayout point_mesh_layout(int B, int N, int F) {
+    const SplitPlan p = split_plan(B, N, F, PM_QBLOCK, PM_TILE, PM_SPLIT_BLOCKS);
+    const size_t bn = (size_t)B * N * 4, part = bn * p.nsplit;
+    Cutter c;
+    return {p, c.take((size_t)B * F * PM_REC * 4), c.take(bn), c.take(bn), c.take(bn), c.take_if(p.nsplit > 1, part),
+            c.take_if(p.nsplit > 1, part), c.off};
+}
+
 int validate_raster(const NrRasterArgs* a, bool need_workspace) {
     if (!a) return fail(NR_ERR_ARGS, "null args");
     if (a->batch_size < 0 || a->num_faces < 0 || a->num_vertices < 0 || a->image_size <= 0)
         return fail(NR_ERR_ARGS, "bad sizes B=%d F=%d V=%d s=%d", a->batch_size, a->num_faces, a->num_vertices,
                     a->image_size);
-    const int S = a->anti_aliasing ? 2 * a->image_size : a->image_size;
+    const int S = internal_size(a->anti_aliasing, a->image_size);
     if (S > 16384) return fail(NR_ERR_ARGS, "image too large (%d internal pixels per side)", S);
     if (nr_num_channels(a->draw_flags) == 0) return fail(NR_ERR_ARGS, "nothing to draw");
     if (a->batch_size > 0 && a->num_faces > 0 && (!a->vertices || !a->faces || !a->face_records))
@@ -29,8 +138,7 @@ int validate_raster(const NrRasterArgs* a, bool need_workspace) {
                                ((long long)a->tex_height * a->tex_width - 1) * std::llabs(a->tex_stride_p) + 1;
         if (span >= (1ll << 31)) return fail(NR_ERR_ARGS, "texture item spans 2^31 elements or more");
     }
-    const Geom g = make_geom(a->num_faces, S);
-    const size_t need = ws_bbox_bytes(a->batch_size, a->num_faces) + ws_mask_bytes(a->batch_size, g) + ws_order_bytes(a->batch_size, g);
+    const size_t need = forward_layout(a->batch_size, a->num_faces, make_geom(a->num_faces, S)).total;
     if (need_workspace && need > 0 && (!a->workspace || a->workspace_bytes < need))
         return fail(NR_ERR_WORKSPACE, "workspace missing or too small");
     return NR_OK;
@@ -48,7 +156,7 @@ Shade make_shade(const NrRasterArgs* a) {
     sh.tv.H = a->tex_height;
     sh.tv.W = a->tex_width;
     sh.tv.t4 = reinterpret_cast<const float4*>(a->textures_packed);
-    sh.tv.HWp = (a->tex_height * a->tex_width + 3) & ~3;
+    sh.tv.HWp = (int)packed_texels(a->tex_height, a->tex_width);
     sh.face_uv = a->face_uv;
     sh.uv_bstride = a->vt_batch_stride ? (long long)a->num_faces * 8 : 0;
     const bool rgb = (a->draw_flags & NR_DRAW_RGB) != 0;

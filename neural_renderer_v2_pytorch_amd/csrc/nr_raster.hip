@@ -27,7 +27,7 @@
 // perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian and
 // flatten regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_adam.h
 // (multi-tensor Adam), nr_attributes.h (per-vertex attribute rendering), nr_point_loss.h (chamfer distance,
-// nearest points and surface sampling), nr_point_mesh.h (point-to-surface distance), nr_host.h (argument checks); this file holds the extern "C" ABI.
+// nearest points and surface sampling), nr_point_mesh.h (point-to-surface distance), nr_host.h (workspace layouts, launch helpers, argument checks); this file holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -88,12 +88,14 @@ int nr_num_channels(int draw_flags) {
 
 size_t nr_hot_acc_bytes(int num_hot) {
     if (num_hot <= 0) return 0;
-    return align_up(hot_sums_floats(num_hot) * 4) + align_up((size_t)num_hot * 8);
+    Cutter c;  // the windows' sums (k_raster_bwd finds the positions hot_sums_floats after them), then the positions
+    c.take(hot_sums_floats(num_hot) * 4);
+    c.take((size_t)num_hot * 8);
+    return c.off;
 }
 
 size_t nr_workspace_bytes(int batch_size, int num_faces, int image_size) {
-    const Geom g = make_geom(num_faces, image_size);
-    return ws_bbox_bytes(batch_size, num_faces) + ws_mask_bytes(batch_size, g) + ws_order_bytes(batch_size, g);
+    return forward_layout(batch_size, num_faces, make_geom(num_faces, image_size)).total;
 }
 
 // A side stream per (host thread, device) for the split forward, with its fork / join events; created
@@ -207,10 +209,11 @@ static int run_face_index(const float* vertices, const int32_t* faces_idx, float
     Geom g = make_geom(F, S);
     g.group = group_for(B, FWD_GROUP);
     g.B = B;
-    int2* bbox = (int2*)ws;
-    uint32_t* mask = (uint32_t*)((char*)ws + ws_bbox_bytes(B, F));
-    uint8_t* bin_part = (uint8_t*)mask + ws_mask_bytes(B, g);
-    int* bin_order = (int*)(bin_part + ws_part_bytes(B, g));
+    const FwdLayout wl = forward_layout(B, F, g);
+    int2* bbox = (int2*)((char*)ws + wl.bbox);
+    uint32_t* mask = (uint32_t*)((char*)ws + wl.mask);
+    uint8_t* bin_part = (uint8_t*)ws + wl.part;
+    int* bin_order = (int*)((char*)ws + wl.order);
     if (B == 0) return NR_OK;
     // forward block size (k_raster_fwd notes): 256 threads when the grid alone fills the chip many
     // times over and the bins are shallow; 1024 when it does not, or when the bins are deep (F per bin
@@ -228,13 +231,13 @@ static int run_face_index(const float* vertices, const int32_t* faces_idx, float
     const long long setup_idle = (long long)((F + SETUP_FACES - 1) / SETUP_FACES) * B * (256 - SETUP_FACES);
     if (pk.out && (F == 0 || pk.n > 32 * setup_idle)) {
         ProfScope _p(P_TEXPACK, st, true);
-        nr_launch(k_tex_pack, dim3((unsigned)((pk.n + 255) / 256)), dim3(256), 0, st, pk);
+        nr_launch(k_tex_pack, grid_1d(pk.n, 256), dim3(256), 0, st, pk);
         const int e = check_launch("k_tex_pack");
         if (e) return e;
         pk.out = nullptr;
     }
-    if (F == 0 && zf.p && hipMemsetAsync(zf.p, 0, (size_t)zf.n16 * 16, st) != hipSuccess)
-        return check_launch("hipMemsetAsync");
+    int e;
+    if (F == 0 && zf.p && !zero_async(zf.p, (size_t)zf.n16 * 16, st, &e)) return e;
 
     // k_shade's work fused into the forward's 256-thread variant (anti-aliasing, no lights or
     // backgrounds): the face-index map is not read back, and there is one launch fewer
@@ -264,11 +267,11 @@ static int run_face_index(const float* vertices, const int32_t* faces_idx, float
                   rgb ? ra->num_vertices_textures : 0, rgb ? ra->faces_textures : nullptr,
                   rgb ? ra->face_uv : nullptr, uv_items, lit ? ra->face_normals : nullptr, pk, zf,
                   ordered ? bin_part : nullptr, B % 8 == 0, sg ? 1 : 0);
-        int e = check_launch("k_face_setup");
+        e = check_launch("k_face_setup");
         if (e) return e;
         if (lit && V > 0) {
             const long long nv = (long long)B * V;
-            nr_launch(k_vertex_normals, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, ra->face_normals,
+            nr_launch(k_vertex_normals, grid_1d(nv, 256), dim3(256), 0, st, ra->face_normals,
                                ra->normal_offsets, ra->normal_faces, ra->vertex_normals, F, V, nv);
             e = check_launch("k_vertex_normals");
             if (e) return e;
@@ -296,16 +299,16 @@ static int run_face_index(const float* vertices, const int32_t* faces_idx, float
     const bool qs = ordered && !side;
     const int lists = B % 8 == 0 ? 8 : 1;
     // each list's count of deep bins (k_bin_order): a deep-first forward either splits or walks quadrants
-    int* split_cnt = ordered ? (int*)((char*)bin_order + align_up((size_t)B * g.nbins * 4)) : nullptr;
+    int* split_cnt = ordered ? (int*)((char*)ws + wl.split_cnt) : nullptr;
     if (ordered) {
         nr_launch(k_bin_order, dim3(lists), dim3(1024), 0, st, bin_part, setup_groups(g), bin_order, B,
                            g.nbins, split_cnt, SPLIT_BUCKET, side ? deep_cap : QS_CAP);
-        const int e = check_launch("k_bin_order");
+        e = check_launch("k_bin_order");
         if (e) return e;
     }
     const int* order = ordered ? bin_order : nullptr;
     // per-bin foreground flags after the halo values (the backward skips background tiles)
-    uint8_t* binfg = (ra && ra->halo) ? (uint8_t*)ra->halo + halo_flags_offset_bytes(B, S, sh.C) : nullptr;
+    uint8_t* binfg = (ra && ra->halo) ? (uint8_t*)ra->halo + halo_layout(B, S, sh.C).flags : nullptr;
     // empty bins leave their -1 face ids unwritten (NrRasterArgs.face_index_sparse): with the fused
     // shading nothing else in this launch reads them, and the backward skips those tiles by the flags
     const int sparse = (ra && ra->face_index_sparse && fuse && binfg) ? 1 : 0;
@@ -337,7 +340,6 @@ static int run_face_index(const float* vertices, const int32_t* faces_idx, float
                                             (order ? NR_LAUNCH_DEEP_FIRST : 0) | (side ? NR_LAUNCH_SPLIT : 0) |
                                             (fwd.dq ? NR_LAUNCH_DEALT_QUARTERS : 0) |
                                             (fwd.part == 3 ? NR_LAUNCH_QUADRANTS : 0)});
-    int e;
     {
         ProfScope _p(P_RASTER, st, side == nullptr);
         if (side) {
@@ -364,7 +366,7 @@ static int run_face_index(const float* vertices, const int32_t* faces_idx, float
     {
         ProfScope _p(P_SHADE, st, true);
         nr_launch(shade_kernel(small, (sh.nl ? 1 : 0) | (sh.bg ? 2 : 0)),
-                  dim3((unsigned)(((long long)s * s + per_block - 1) / per_block), B), dim3(256), 0, st, face_records, fim,
+                  grid_1d((long long)s * s, per_block, B), dim3(256), 0, st, face_records, fim,
                   F, S, sh, ra->anti_aliasing, images, ra->halo);
     }
     return check_launch("k_shade");
@@ -391,7 +393,7 @@ int nr_compute_weight_map(const float* faces, const int32_t* face_index_map, flo
         return fail(NR_ERR_ARGS, "bad sizes B=%d F=%d S=%d", batch_size, num_faces, image_size);
     const long long n = (long long)batch_size * image_size * image_size;
     if (n == 0) return NR_OK;
-    nr_launch(k_weight_map, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, faces,
+    nr_launch(k_weight_map, grid_1d(n, 256), dim3(256), 0, (hipStream_t)stream, faces,
                        face_index_map, weight_map, num_faces, image_size, n);
     return check_launch("k_weight_map");
 }
@@ -400,7 +402,7 @@ int nr_mask_foreground_forward(const int32_t* face_index, const float* data_in, 
                                void* stream) {
     if (n < 0 || dim < 0) return fail(NR_ERR_ARGS, "bad sizes");
     if (n == 0) return NR_OK;
-    nr_launch(k_mask_fg, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, face_index,
+    nr_launch(k_mask_fg, grid_1d(n, 256), dim3(256), 0, (hipStream_t)stream, face_index,
                        data_in, data_out, n, dim);
     return check_launch("k_mask_fg");
 }
@@ -416,7 +418,7 @@ int nr_differentiation_backward(const float* images, const float* grad, float* g
     const long long n = (long long)batch_size * height * width;
     if (n == 0) return NR_OK;
     const float step = (float)(2. / height);
-    nr_launch(k_diff_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, images, grad,
+    nr_launch(k_diff_bwd, grid_1d(n, 256), dim3(256), 0, (hipStream_t)stream, images, grad,
                        grad_xy, height, width, channels, step, n);
     return check_launch("k_diff_bwd");
 }
@@ -433,7 +435,7 @@ int nr_rasterize_forward(const NrRasterArgs* a, float* images, void* stream) {
         pk.sc = (int)a->tex_stride_c;
         pk.sp = (int)a->tex_stride_p;
         pk.HW = a->tex_height * a->tex_width;
-        pk.HWp = (pk.HW + 3) & ~3;
+        pk.HWp = (int)packed_texels(a->tex_height, a->tex_width);
         pk.out = reinterpret_cast<float4*>(a->textures_packed);
         pk.n = (long long)tex_items * pk.HWp;
     }
@@ -445,7 +447,7 @@ int nr_rasterize_forward(const NrRasterArgs* a, float* images, void* stream) {
         zf.p = reinterpret_cast<float4*>(a->bwd_workspace);
         zf.n16 = (long long)(a->bwd_workspace_bytes / 16);
     }
-    const int S = a->anti_aliasing ? 2 * a->image_size : a->image_size;
+    const int S = internal_size(a->anti_aliasing, a->image_size);
     return run_face_index(a->vertices, a->faces, a->face_records, a->face_index, a->batch_size, a->num_vertices,
                           a->num_faces, S, a->near, a->far, a->draw_backside, a->depth_min_delta, a->workspace,
                           a->workspace_bytes, (hipStream_t)stream, a, images, pk, zf);
@@ -453,28 +455,17 @@ int nr_rasterize_forward(const NrRasterArgs* a, float* images, void* stream) {
 
 size_t nr_texture_packed_bytes(int texture_items, int tex_height, int tex_width) {
     if (texture_items <= 0 || tex_height <= 0 || tex_width <= 0) return 0;
-    return (size_t)texture_items * ((((size_t)tex_height * tex_width) + 3) & ~size_t(3)) * 16;
+    return (size_t)texture_items * packed_texels(tex_height, tex_width) * 16;
 }
 
 size_t nr_halo_bytes(int batch_size, int image_size, int anti_aliasing, int draw_flags) {
-    const int S = anti_aliasing ? 2 * image_size : image_size;
     if (batch_size <= 0 || image_size <= 0) return 0;
-    const Geom g = make_geom(0, S);
-    return (size_t)halo_flags_offset_bytes(batch_size, S, nr_num_channels(draw_flags)) +
-           (((size_t)batch_size * g.nbins + 3) & ~size_t(3));
+    return halo_layout(batch_size, internal_size(anti_aliasing, image_size), nr_num_channels(draw_flags)).total;
 }
 
-// backward workspace: [gF: B F 9 face-corner floats][g4: Bt HWp RGBA texel rows]
-// [lights: gN: B F 9][gU: B V 3]; everything before gU starts at zero (one memset, or the forward's
-// setup zeroed it: NrRasterArgs.bwd_workspace)
 size_t nr_backward_workspace_bytes(int batch_size, int num_faces, int num_vertices, int texture_items,
                                    int tex_height, int tex_width, int num_lights) {
-    const size_t hw = (size_t)tex_height * tex_width, hwp = (hw + 3) & ~size_t(3);
-    size_t n = align_up((size_t)batch_size * num_faces * 9 * 4);
-    if (texture_items > 0) n += align_up((size_t)texture_items * hwp * 16);
-    if (num_lights > 0)
-        n += align_up((size_t)batch_size * num_faces * 9 * 4) + align_up((size_t)batch_size * num_vertices * 3 * 4);
-    return n;
+    return backward_layout(batch_size, num_faces, num_vertices, texture_items, tex_height, tex_width, num_lights > 0).total;
 }
 
 int nr_rasterize_backward(const NrRasterArgs* a, const float* grad_images, float* grad_vertices, float* grad_textures,
@@ -486,8 +477,7 @@ int nr_rasterize_backward(const NrRasterArgs* a, const float* grad_images, float
         // (tex_stride_b == 0: one item) gets zeros; per-item textures and backgrounds have no items
         if ((a->draw_flags & NR_DRAW_RGB) && grad_textures && !a->tex_stride_b) {
             const size_t n = (size_t)3 * a->tex_height * a->tex_width * sizeof(float);
-            if (n && hipMemsetAsync(grad_textures, 0, n, (hipStream_t)stream) != hipSuccess)
-                return check_launch("hipMemsetAsync");
+            if (n && !zero_async(grad_textures, n, (hipStream_t)stream, &e)) return e;
         }
         return NR_OK;
     }
@@ -511,41 +501,37 @@ int nr_rasterize_backward(const NrRasterArgs* a, const float* grad_images, float
                      !a->backgrounds;
     if (hot && (a->num_hot > NR_HOT_MAX || !a->hot_acc || ((uintptr_t)a->hot_acc & 15)))
         return fail(NR_ERR_ARGS, "face_hot: num_hot %d (at most %d) needs a 16-byte aligned hot_acc", a->num_hot, NR_HOT_MAX);
-    const size_t need = nr_backward_workspace_bytes(a->batch_size, a->num_faces, a->num_vertices, tex_items,
-                                                    a->tex_height, a->tex_width, lit ? a->num_lights : 0);
-    if (need > 0 && (!workspace || workspace_bytes < need))
+    const BwdLayout wl = backward_layout(a->batch_size, a->num_faces, a->num_vertices, tex_items, a->tex_height,
+                                         a->tex_width, lit);
+    if (wl.total > 0 && (!workspace || workspace_bytes < wl.total))
         return fail(NR_ERR_WORKSPACE, "backward workspace missing or too small");
     hipStream_t st = (hipStream_t)stream;
-    const int S = a->anti_aliasing ? 2 * a->image_size : a->image_size;
+    const int S = internal_size(a->anti_aliasing, a->image_size);
     Geom g = make_geom(a->num_faces, S);
     const bool hot_texels = rgb && !a->tex_stride_b &&
                             (long long)a->tex_height * a->tex_width > BWD_HOT_TEXELS_PER_FACE * a->num_faces;
     g.group = group_for(a->batch_size, hot_texels ? BWD_GROUP_TEX : BWD_GROUP);
     const int HW = a->tex_height * a->tex_width;
-    const int HWp = (HW + 3) & ~3;
+    const int HWp = (int)packed_texels(a->tex_height, a->tex_width);
     char* w = (char*)workspace;
-    float* gF = (float*)w;
-    w += align_up((size_t)a->batch_size * a->num_faces * 9 * 4);
-    float* g4 = rgb ? (float*)w : nullptr;
-    if (rgb) w += align_up((size_t)tex_items * HWp * 16);
-    float* gN = lit ? (float*)w : nullptr;
-    float* gU = lit ? (float*)(w + align_up((size_t)a->batch_size * a->num_faces * 9 * 4)) : nullptr;
-    // gU is fully written by k_vnormal_bwd; the accumulators before it start at zero
-    const size_t zero_bytes = lit ? (size_t)((char*)gU - (char*)workspace) : need;
-    // ... unless the caller states, for this call, that the forward zeroed them (NrRasterArgs.bwd_workspace)
+    float* gF = (float*)(w + wl.gF);
+    float* g4 = rgb ? (float*)(w + wl.g4) : nullptr;
+    float* gN = lit ? (float*)(w + wl.gN) : nullptr;
+    float* gU = lit ? (float*)(w + wl.gU) : nullptr;
+    // the accumulators before gU start at zero, unless the caller states, for this call, that the
+    // forward zeroed them (NrRasterArgs.bwd_workspace)
     const bool prezeroed = workspace_zeroed != 0;
-    if (prezeroed && zero_bytes > 0 && (a->bwd_workspace != workspace || a->bwd_workspace_bytes < zero_bytes))
+    if (prezeroed && wl.zero_bytes > 0 && (a->bwd_workspace != workspace || a->bwd_workspace_bytes < wl.zero_bytes))
         return fail(NR_ERR_ARGS, "workspace_zeroed = 1 needs args->bwd_workspace == workspace with at least %zu bytes "
-                                 "(the buffer the forward zeroed)", zero_bytes);
-    if (zero_bytes > 0 && !prezeroed && hipMemsetAsync(workspace, 0, zero_bytes, st) != hipSuccess)
-        return check_launch("hipMemsetAsync");
+                                 "(the buffer the forward zeroed)", wl.zero_bytes);
+    if (wl.zero_bytes > 0 && !prezeroed && !zero_async(workspace, wl.zero_bytes, st, &e)) return e;
     if (hot) {
         // hot_acc starts at zero: the forward zeroed it when it lies inside the zeroed bwd_workspace
         const size_t hb = nr_hot_acc_bytes(a->num_hot);
         const char* hz = (const char*)a->hot_acc;
         const bool in_zeroed = prezeroed && hz >= (const char*)a->bwd_workspace &&
                                hz + hb <= (const char*)a->bwd_workspace + a->bwd_workspace_bytes;
-        if (!in_zeroed && hipMemsetAsync(a->hot_acc, 0, hb, st) != hipSuccess) return check_launch("hipMemsetAsync");
+        if (!in_zeroed && !zero_async(a->hot_acc, hb, st, &e)) return e;
     }
     BwdArgs ba;
     ba.face_records = a->face_records;
@@ -554,7 +540,7 @@ int nr_rasterize_backward(const NrRasterArgs* a, const float* grad_images, float
     ba.grad_faces = gF;
     ba.grad_tex = g4;
     ba.halo = a->halo;
-    ba.binfg = a->halo ? (const uint8_t*)a->halo + halo_flags_offset_bytes(a->batch_size, S, nr_num_channels(a->draw_flags))
+    ba.binfg = a->halo ? (const uint8_t*)a->halo + halo_layout(a->batch_size, S, nr_num_channels(a->draw_flags)).flags
                        : nullptr;
     ba.grad_normals = gN;
     ba.grad_bg = (a->draw_flags & NR_DRAW_RGB) && a->backgrounds ? a->grad_backgrounds : nullptr;
@@ -596,13 +582,13 @@ int nr_rasterize_backward(const NrRasterArgs* a, const float* grad_images, float
     const long long nv = (long long)a->batch_size * a->num_vertices;
     if (lit && nv > 0) {
         // lights: vertex-normal gradients -> face normals -> corner gradients (added into gF)
-        nr_launch(k_vnormal_bwd, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, gN, a->vertex_offsets,
+        nr_launch(k_vnormal_bwd, grid_1d(nv, 256), dim3(256), 0, st, gN, a->vertex_offsets,
                            a->vertex_faces, a->vertex_normals, gU, a->num_faces, a->num_vertices, nv);
         e = check_launch("k_vnormal_bwd");
         if (e) return e;
         const long long nf = (long long)a->batch_size * a->num_faces;
         if (nf > 0) {
-            nr_launch(k_fnormal_bwd, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, st, a->face_records,
+            nr_launch(k_fnormal_bwd, grid_1d(nf, 256), dim3(256), 0, st, a->face_records,
                                a->faces, gU, gF, a->num_faces, a->num_vertices, nf);
             e = check_launch("k_fnormal_bwd");
             if (e) return e;
@@ -633,7 +619,7 @@ int nr_rasterize_backward(const NrRasterArgs* a, const float* grad_images, float
     if (to.out && to.n > 0 && !carry) {
         {
             ProfScope _p(P_TEXOUT, st, true);
-            nr_launch(k_tex_out, dim3((unsigned)((to.n + 255) / 256)), dim3(256), 0, st, to);
+            nr_launch(k_tex_out, grid_1d(to.n, 256), dim3(256), 0, st, to);
         }
         e = check_launch("k_tex_out");
     }
@@ -655,15 +641,15 @@ int nr_rasterize_backward_params(const NrRasterArgs* a, const float* grad_images
     const long long gvt_bstride = (long long)a->num_vertices_textures * 2;
     if (uv) {
         const size_t n = (size_t)(a->vt_batch_stride ? B : 1) * gvt_bstride * sizeof(float);
-        if (n && hipMemsetAsync(grad_vertices_textures, 0, n, st) != hipSuccess) return check_launch("hipMemsetAsync");
+        if (n && !zero_async(grad_vertices_textures, n, st, &e)) return e;
     }
     if (lgt) {
         const size_t n = (size_t)a->num_lights * B * NR_LIGHT_FLOATS * sizeof(float);
-        if (n && hipMemsetAsync(grad_lights, 0, n, st) != hipSuccess) return check_launch("hipMemsetAsync");
+        if (n && !zero_async(grad_lights, n, st, &e)) return e;
     }
     if (B == 0 || a->num_faces == 0 || !(uv || lgt)) return NR_OK;
     if (!grad_images) return fail(NR_ERR_ARGS, "null grad_images");
-    const int S = a->anti_aliasing ? 2 * a->image_size : a->image_size;
+    const int S = internal_size(a->anti_aliasing, a->image_size);
     BwdArgs ba = {};
     ba.face_records = a->face_records;
     ba.fim = a->face_index;
@@ -672,7 +658,7 @@ int nr_rasterize_backward_params(const NrRasterArgs* a, const float* grad_images
     ba.aa = a->anti_aliasing;
     ba.s = a->image_size;
     const Shade sh = make_shade(a);  // the lights shade (cw) the uv gradient even without light gradients
-    const dim3 grid((unsigned)(((long long)S * S + 255) / 256), B);
+    const dim3 grid = grid_1d((long long)S * S, 256, B);
     auto kernel = k_param_bwd<true, true>;  // <UV, LGT>: at least one of the two is wanted here
     if (!lgt) kernel = k_param_bwd<true, false>;
     if (!uv) kernel = k_param_bwd<false, true>;
@@ -697,7 +683,7 @@ int nr_camera_forward(const NrCameraArgs* c, float* out, void* stream) {
     const long long n = (long long)c->batch_size * c->num_vertices;
     if (n == 0) return NR_OK;
     if (!out) return fail(NR_ERR_ARGS, "null output");
-    nr_launch(k_camera_fwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, *c, out);
+    nr_launch(k_camera_fwd, grid_1d(n, 256), dim3(256), 0, (hipStream_t)stream, *c, out);
     return check_launch("k_camera_fwd");
 }
 
@@ -709,14 +695,13 @@ int nr_camera_backward(const NrCameraArgs* c, const float* grad_out, float* grad
     const bool want_eye = grad_eye && c->mode != NR_CAMERA_NONE;
     const int neye = c->eye_batch_stride ? c->batch_size : 1;
     if (grad_eye && !want_eye) {  // no eye in the transform: zero gradient
-        if (hipMemsetAsync(grad_eye, 0, (size_t)neye * 3 * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");
+        if (!zero_async(grad_eye, (size_t)neye * 3 * 4, st, &e)) return e;
         grad_eye = nullptr;
     }
     const long long nv = (long long)(c->v_batch_stride ? c->batch_size : 1) * c->num_vertices;
     if (c->batch_size == 0) {
-        if (grad_vertices && nv > 0 && hipMemsetAsync(grad_vertices, 0, (size_t)nv * 12, st) != hipSuccess)
-            return check_launch("hipMemsetAsync");
-        if (want_eye && hipMemsetAsync(grad_eye, 0, (size_t)neye * 12, st) != hipSuccess) return check_launch("hipMemsetAsync");
+        if (grad_vertices && nv > 0 && !zero_async(grad_vertices, (size_t)nv * 12, st, &e)) return e;
+        if (want_eye && !zero_async(grad_eye, (size_t)neye * 12, st, &e)) return e;
         return NR_OK;
     }
     if (!grad_out && (grad_vertices || want_eye)) return fail(NR_ERR_ARGS, "null grad_out");
@@ -725,16 +710,16 @@ int nr_camera_backward(const NrCameraArgs* c, const float* grad_out, float* grad
         if (!workspace || workspace_bytes < nr_camera_workspace_bytes(c->batch_size))
             return fail(NR_ERR_WORKSPACE, "camera workspace missing or too small");
         acc = (float*)workspace;
-        if (hipMemsetAsync(acc, 0, (size_t)c->batch_size * 12 * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");
+        if (!zero_async(acc, (size_t)c->batch_size * 12 * 4, st, &e)) return e;
     }
     if ((grad_vertices || acc) && nv > 0) {
-        nr_launch(k_camera_bwd, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, *c, grad_out, grad_vertices, acc);
+        nr_launch(k_camera_bwd, grid_1d(nv, 256), dim3(256), 0, st, *c, grad_out, grad_vertices, acc);
         e = check_launch("k_camera_bwd");
         if (e) return e;
     }
     if (want_eye) {
-        if (nv == 0 && hipMemsetAsync(acc, 0, (size_t)c->batch_size * 12 * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");
-        nr_launch(k_camera_eye, dim3((unsigned)((neye + 63) / 64)), dim3(64), 0, st, *c, acc, grad_eye);
+        if (nv == 0 && !zero_async(acc, (size_t)c->batch_size * 12 * 4, st, &e)) return e;
+        nr_launch(k_camera_eye, grid_1d(neye, 64), dim3(64), 0, st, *c, acc, grad_eye);
         e = check_launch("k_camera_eye");
     }
     return e;
@@ -787,7 +772,7 @@ int nr_projection_backward(const NrProjectionArgs* p, const float* grad_out, flo
             {grad_R, (size_t)(p->r_batch_stride ? B : 1) * 9},           {grad_t, (size_t)(p->t_batch_stride ? B : 1) * 3},
             {grad_dist, (size_t)(p->dist_batch_stride ? B : 1) * 5}};
         for (const auto& f : fill)
-            if (f.g && f.n && hipMemsetAsync(f.g, 0, f.n * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");
+            if (f.g && f.n && !zero_async(f.g, f.n * 4, st, &e)) return e;
         return NR_OK;
     }
     const bool params = grad_K || grad_R || grad_t || grad_dist;
@@ -873,9 +858,9 @@ int nr_flatten_forward(const float* vertices, const int32_t* edges, int batch_si
         if (V == 0 || !vertices || !edges) return fail(NR_ERR_ARGS, "edges without vertices");
         if (!workspace || workspace_bytes < nr_mesh_loss_workspace_bytes(B, E2))
             return fail(NR_ERR_WORKSPACE, "mesh loss workspace missing or too small");
-        const dim3 grid((unsigned)(B * nblk));
-        if (records) nr_launch(k_flat_fwd<true>, grid, dim3(ML_BLOCK), 0, st, vertices, edges, V, E2, nblk, eps, records, (float*)workspace);
-        else nr_launch(k_flat_fwd<false>, grid, dim3(ML_BLOCK), 0, st, vertices, edges, V, E2, nblk, eps, records, (float*)workspace);
+        const auto kernel = records ? k_flat_fwd<true> : k_flat_fwd<false>;
+        nr_launch(kernel, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, st, vertices, edges, V, E2, nblk, eps, records,
+                  (float*)workspace);
         e = check_launch("k_flat_fwd");
         if (e) return e;
     }
@@ -898,29 +883,6 @@ int nr_flatten_backward(const float* records, const int32_t* edge_offsets, const
 }
 
 // ---- point losses (nr_point_loss.h) ----
-// How one direction of a chamfer launch is cut: query blocks per item, and target ranges per query block
-// (more than one -- the split path -- while the direction has fewer than PL_SPLIT_BLOCKS blocks and every
-// range still holds at least a full tile of targets: few queries against many targets would otherwise
-// leave most of the chip idle).
-struct PlPlan {
-    int nqb, nsplit;
-};
-static PlPlan pl_plan(int B, int nq, int nt) {
-    PlPlan p;
-    p.nqb = (int)(((long long)nq + PL_QBLOCK - 1) / PL_QBLOCK);
-    const long long have = (long long)B * p.nqb;
-    const long long want = (PL_SPLIT_BLOCKS + have - 1) / have, most = nt / PL_TILE;
-    p.nsplit = (int)(want < most ? want : most);
-    if (p.nsplit < 1) p.nsplit = 1;
-    return p;
-}
-// workspace floats of one direction: the per-query minima [B, nq] and, on the split path, the partial
-// (d2, j) pairs [B, nsplit, nq] twice
-static size_t pl_dir_bytes(int B, int nq, int nt) {
-    const PlPlan p = pl_plan(B, nq, nt);
-    return align_up((size_t)B * nq * 4) + (p.nsplit > 1 ? 2 * align_up((size_t)B * p.nsplit * nq * 4) : 0);
-}
-
 static int validate_chamfer(int B, int N, int M, int directions) {
     if (B < 0) return fail(NR_ERR_ARGS, "bad batch size B=%d", B);
     if (N <= 0 || M <= 0) return fail(NR_ERR_ARGS, "empty point set N=%d M=%d (both must be at least 1)", N, M);
@@ -932,8 +894,8 @@ static int validate_chamfer(int B, int N, int M, int directions) {
 
 size_t nr_chamfer_workspace_bytes(int batch_size, int num_x, int num_y, int directions) {
     if (batch_size <= 0 || num_x <= 0 || num_y <= 0) return 0;
-    return ((directions & NR_CHAMFER_X_TO_Y) ? pl_dir_bytes(batch_size, num_x, num_y) : 0) +
-           ((directions & NR_CHAMFER_Y_TO_X) ? pl_dir_bytes(batch_size, num_y, num_x) : 0);
+    return ((directions & NR_CHAMFER_X_TO_Y) ? chamfer_layout(batch_size, num_x, num_y).total : 0) +
+           ((directions & NR_CHAMFER_Y_TO_X) ? chamfer_layout(batch_size, num_y, num_x).total : 0);
 }
 
 int nr_chamfer_forward(const float* x, const float* y, long long y_batch_stride, int batch_size, int num_x, int num_y,
@@ -959,24 +921,23 @@ int nr_chamfer_forward(const float* x, const float* y, long long y_batch_stride,
     for (int k = 0; k < 2; k++) {
         if (!(k == 0 ? xy : yx)) continue;
         const int nq = k == 0 ? N : M, nt = k == 0 ? M : N;
-        const PlPlan p = pl_plan(B, nq, nt);
+        const ChamferLayout wl = chamfer_layout(B, nq, nt);
+        const SplitPlan p = wl.plan;
         PlDir& r = d[nd];
         r.q = k == 0 ? x : y, r.t = k == 0 ? y : x;
         r.q_stride = k == 0 ? (long long)N * 3 : y_batch_stride;
         r.t_stride = k == 0 ? y_batch_stride : (long long)N * 3;
         r.nq = nq, r.nt = nt, r.nqb = p.nqb, r.nsplit = p.nsplit;
         float* user = k == 0 ? dist2_xy : dist2_yx;
-        fin_d[nd] = user ? user : (float*)ws;
-        ws += align_up((size_t)B * nq * 4);
+        fin_d[nd] = user ? user : (float*)(ws + wl.minima);
         fin_j[nd] = k == 0 ? index_xy : index_yx;
         if (p.nsplit > 1) {
-            const size_t part = align_up((size_t)B * p.nsplit * nq * 4);
-            r.dist2 = (float*)ws, r.index = (int32_t*)(ws + part);
-            ws += 2 * part;
+            r.dist2 = (float*)(ws + wl.part_d2), r.index = (int32_t*)(ws + wl.part_j);
             flags |= k == 0 ? NR_LAUNCH_SPLIT_X_TO_Y : NR_LAUNCH_SPLIT_Y_TO_X;
         } else {
             r.dist2 = fin_d[nd], r.index = fin_j[nd];
         }
+        ws += wl.total;
         nd++;
     }
     const int blocks0 = d[0].nqb * d[0].nsplit, blocks1 = nd > 1 ? d[1].nqb * d[1].nsplit : 0;
@@ -987,8 +948,8 @@ int nr_chamfer_forward(const float* x, const float* y, long long y_batch_stride,
     if (e) return e;
     for (int k = 0; k < nd; k++) {
         if (d[k].nsplit == 1) continue;
-        nr_launch(k_chamfer_combine, dim3((unsigned)((d[k].nq + PL_BLOCK - 1) / PL_BLOCK), (unsigned)B), dim3(PL_BLOCK), 0, st,
-                  (const float*)d[k].dist2, (const int32_t*)d[k].index, d[k].nq, d[k].nsplit, fin_d[k], fin_j[k]);
+        nr_launch(k_chamfer_combine, grid_1d(d[k].nq, PL_BLOCK, B), dim3(PL_BLOCK), 0, st, (const float*)d[k].dist2,
+                  (const int32_t*)d[k].index, d[k].nq, d[k].nsplit, fin_d[k], fin_j[k]);
         e = check_launch("k_chamfer_combine");
         if (e) return e;
     }
@@ -1060,7 +1021,7 @@ int nr_sample_points_forward(const float* vertices, const int32_t* faces, const 
     e = check_launch("k_sample_scan");
     if (e) return e;
     const long long n = (long long)B * S;
-    nr_launch(k_sample_points, dim3((unsigned)((n + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, st, vertices, faces, u,
+    nr_launch(k_sample_points, grid_1d(n, PL_BLOCK), dim3(PL_BLOCK), 0, st, vertices, faces, u,
               (const float*)workspace, V, F, S, n, points, face, weights);
     return check_launch("k_sample_points");
 }
@@ -1073,27 +1034,14 @@ int nr_sample_points_backward(const int32_t* faces, const int32_t* face, const f
     if (B == 0) return NR_OK;
     if (!faces || !face || !weights || !grad_points || !grad_vertices) return fail(NR_ERR_ARGS, "null pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(grad_vertices, 0, (size_t)B * V * 3 * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");
+    if (!zero_async(grad_vertices, (size_t)B * V * 3 * 4, st, &e)) return e;
     const long long n = (long long)B * S;
-    nr_launch(k_sample_points_bwd, dim3((unsigned)((n + PL_BLOCK - 1) / PL_BLOCK)), dim3(PL_BLOCK), 0, st, faces, face, weights,
+    nr_launch(k_sample_points_bwd, grid_1d(n, PL_BLOCK), dim3(PL_BLOCK), 0, st, faces, face, weights,
               grad_points, V, S, n, grad_vertices);
     return check_launch("k_sample_points_bwd");
 }
 
 // ---- point-to-surface distance (nr_point_mesh.h) ----
-// How a launch is cut, as pl_plan cuts a chamfer direction: query blocks per item, and face ranges per
-// query block (the split path) while the launch has fewer than PM_SPLIT_BLOCKS blocks and every range
-// still holds at least a full tile of faces (results do not depend on the cut: nr_point_mesh.h).
-static PlPlan pm_plan(int B, int N, int F) {
-    PlPlan p;
-    p.nqb = (int)(((long long)N + PM_QBLOCK - 1) / PM_QBLOCK);
-    const long long have = (long long)B * p.nqb;
-    const long long want = (PM_SPLIT_BLOCKS + have - 1) / have, most = F / PM_TILE;
-    p.nsplit = (int)(want < most ? want : most);
-    if (p.nsplit < 1) p.nsplit = 1;
-    return p;
-}
-
 static int validate_point_mesh(int B, int N, int V, int F) {
     if (B < 0) return fail(NR_ERR_ARGS, "bad batch size B=%d", B);
     if (N <= 0 || F <= 0 || V <= 0) return fail(NR_ERR_ARGS, "empty input N=%d F=%d V=%d (each must be at least 1)", N, F, V);
@@ -1103,14 +1051,9 @@ static int validate_point_mesh(int B, int N, int V, int F) {
     return NR_OK;
 }
 
-// records [B, F, PM_REC], the nearest face [B, N], the loop's and the finish's dist2 [B, N] each, and on the
-// split path the partial (d2, f) pairs [B, nsplit, N] twice
 size_t nr_point_mesh_workspace_bytes(int batch_size, int num_points, int num_faces) {
     if (batch_size <= 0 || num_points <= 0 || num_faces <= 0) return 0;
-    const PlPlan p = pm_plan(batch_size, num_points, num_faces);
-    const size_t bn = align_up((size_t)batch_size * num_points * 4);
-    return align_up((size_t)batch_size * num_faces * PM_REC * 4) + 3 * bn +
-           (p.nsplit > 1 ? 2 * align_up((size_t)batch_size * p.nsplit * num_points * 4) : 0);
+    return point_mesh_layout(batch_size, num_points, num_faces).total;
 }
 
 int nr_point_mesh_forward(const float* points, long long points_batch_stride, const float* vertices, const int32_t* faces,
@@ -1126,23 +1069,20 @@ int nr_point_mesh_forward(const float* points, long long points_batch_stride, co
     if (!workspace || workspace_bytes < nr_point_mesh_workspace_bytes(B, N, F))
         return fail(NR_ERR_ARGS, "point_mesh workspace missing or too small");
     hipStream_t st = (hipStream_t)stream;
-    const PlPlan p = pm_plan(B, N, F);
-    const size_t bn = align_up((size_t)B * N * 4);
+    const PointMeshLayout wl = point_mesh_layout(B, N, F);
+    const SplitPlan p = wl.plan;
     char* ws = (char*)workspace;
-    float* records = (float*)ws;
-    ws += align_up((size_t)B * F * PM_REC * 4);
-    int32_t* nearest = (int32_t*)ws;
-    float* loop_d2 = (float*)(ws + bn);
-    float* fin_d2 = dist2 ? dist2 : (float*)(ws + 2 * bn);
-    ws += 3 * bn;
-    nr_launch(k_point_face_records, dim3((unsigned)((F + PL_BLOCK - 1) / PL_BLOCK), (unsigned)B), dim3(PL_BLOCK), 0, st, vertices, faces,
-              V, F, records);
+    float* records = (float*)(ws + wl.records);
+    int32_t* nearest = (int32_t*)(ws + wl.nearest);
+    float* loop_d2 = (float*)(ws + wl.loop_d2);
+    float* fin_d2 = dist2 ? dist2 : (float*)(ws + wl.fin_d2);
+    nr_launch(k_point_face_records, grid_1d(F, PL_BLOCK, B), dim3(PL_BLOCK), 0, st, vertices, faces, V, F, records);
     e = check_launch("k_point_face_records");
     if (e) return e;
     PmArgs d;
     d.points = points, d.p_stride = points_batch_stride, d.records = records, d.N = N, d.F = F, d.nsplit = p.nsplit;
     if (p.nsplit > 1) {
-        d.dist2 = (float*)ws, d.face = (int32_t*)(ws + align_up((size_t)B * p.nsplit * N * 4));
+        d.dist2 = (float*)(ws + wl.part_d2), d.face = (int32_t*)(ws + wl.part_f);
     } else {
         d.dist2 = loop_d2, d.face = nearest;
     }
@@ -1150,7 +1090,7 @@ int nr_point_mesh_forward(const float* points, long long points_batch_stride, co
     g_last_point_mesh.store(LaunchRec{PL_BLOCK, p.nsplit > 1 ? NR_LAUNCH_SPLIT_FACES : 0});
     e = check_launch("k_point_face_nn");
     if (e) return e;
-    const dim3 per_point((unsigned)((N + PL_BLOCK - 1) / PL_BLOCK), (unsigned)B);
+    const dim3 per_point = grid_1d(N, PL_BLOCK, B);
     if (p.nsplit > 1) {
         nr_launch(k_chamfer_combine, per_point, dim3(PL_BLOCK), 0, st, (const float*)d.dist2, (const int32_t*)d.face, N, p.nsplit,
                   loop_d2, nearest);
@@ -1176,8 +1116,8 @@ int nr_point_mesh_backward(const float* points, long long points_batch_stride, c
     if (B == 0 || (!grad_points && !grad_vertices)) return NR_OK;
     if (!points || !vertices || !faces || !face || !weights || !grad_loss) return fail(NR_ERR_ARGS, "null pointer");
     hipStream_t st = (hipStream_t)stream;
-    if (grad_vertices && hipMemsetAsync(grad_vertices, 0, (size_t)B * V * 3 * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");
-    nr_launch(k_point_mesh_bwd, dim3((unsigned)((N + PL_BLOCK - 1) / PL_BLOCK), (unsigned)B), dim3(PL_BLOCK), 0, st, points,
+    if (grad_vertices && !zero_async(grad_vertices, (size_t)B * V * 3 * 4, st, &e)) return e;
+    nr_launch(k_point_mesh_bwd, grid_1d(N, PL_BLOCK, B), dim3(PL_BLOCK), 0, st, points,
               points_batch_stride, vertices, faces, face, weights, grad_loss, N, V, grad_points, grad_vertices);
     return check_launch("k_point_mesh_bwd");
 }
@@ -1225,7 +1165,7 @@ int nr_pointwise_loss_forward(const float* images, long long image_stride, const
     if (!loss) return fail(NR_ERR_ARGS, "null loss");
     hipStream_t st = (hipStream_t)stream;
     if (N == 0) {
-        if (hipMemsetAsync(loss, 0, (size_t)B * 4, st) != hipSuccess) return check_launch("hipMemsetAsync");
+        if (!zero_async(loss, (size_t)B * 4, st, &e)) return e;
         return NR_OK;
     }
     ILPointwise a;
@@ -1274,8 +1214,8 @@ int nr_iou_loss_forward(const float* images, long long image_stride, const float
         const float one = 1.f - 0.f / (0.f + eps);  // 1, or NaN with eps == 0 as the formula has it
         int bits;
         memcpy(&bits, &one, 4);
-        if (hipMemsetAsync(sums, 0, (size_t)B * 8, st) != hipSuccess || hipMemsetD32Async((hipDeviceptr_t)loss, bits, (size_t)B, st) != hipSuccess)
-            return check_launch("hipMemsetAsync");
+        if (!zero_async(sums, (size_t)B * 8, st, &e)) return e;
+        if (hipMemsetD32Async((hipDeviceptr_t)loss, bits, (size_t)B, st) != hipSuccess) return check_launch("hipMemsetAsync");
         return NR_OK;
     }
     if (!images || !targets) return fail(NR_ERR_ARGS, "null images or targets");
@@ -1284,10 +1224,9 @@ int nr_iou_loss_forward(const float* images, long long image_stride, const float
         return fail(NR_ERR_WORKSPACE, "image loss workspace missing or too small");
     const int nchunk = (int)il_chunks(N);
     const dim3 grid((unsigned)(B * nchunk));
-    if (il_aligned(images, image_stride, B) && il_aligned(targets, target_stride, B))
-        nr_launch(k_iou_fwd<4>, grid, dim3(IL_BLOCK), 0, st, images, image_stride, targets, target_stride, N, nchunk, (float*)workspace);
-    else
-        nr_launch(k_iou_fwd<1>, grid, dim3(IL_BLOCK), 0, st, images, image_stride, targets, target_stride, N, nchunk, (float*)workspace);
+    const bool vec = il_aligned(images, image_stride, B) && il_aligned(targets, target_stride, B);
+    nr_launch(vec ? k_iou_fwd<4> : k_iou_fwd<1>, grid, dim3(IL_BLOCK), 0, st, images, image_stride, targets, target_stride, N, nchunk,
+              (float*)workspace);
     e = check_launch("k_iou_fwd");
     if (e) return e;
     nr_launch(k_iou_finish, dim3((unsigned)B), dim3(IL_BLOCK), 0, st, (const float*)workspace, nchunk, eps, sums, loss);
@@ -1305,10 +1244,9 @@ int nr_iou_loss_backward(const float* targets, long long target_stride, const fl
     const int nchunk = (int)il_chunks(N);
     const dim3 grid((unsigned)(B * nchunk));
     hipStream_t st = (hipStream_t)stream;
-    if (il_aligned(targets, target_stride, B) && il_aligned(grad_images, N, B))
-        nr_launch(k_iou_bwd<4>, grid, dim3(IL_BLOCK), 0, st, targets, target_stride, sums, grad_loss, eps, N, nchunk, grad_images);
-    else
-        nr_launch(k_iou_bwd<1>, grid, dim3(IL_BLOCK), 0, st, targets, target_stride, sums, grad_loss, eps, N, nchunk, grad_images);
+    const bool vec = il_aligned(targets, target_stride, B) && il_aligned(grad_images, N, B);
+    nr_launch(vec ? k_iou_bwd<4> : k_iou_bwd<1>, grid, dim3(IL_BLOCK), 0, st, targets, target_stride, sums, grad_loss, eps, N, nchunk,
+              grad_images);
     return check_launch("k_iou_bwd");
 }
 
@@ -1370,8 +1308,7 @@ int nr_adam_step(const NrAdamArgs* args, void* stream) {
         if (blocks > 0) {
             up.c1 = (float)(1.0 - args->beta1), up.c2 = (float)(1.0 - args->beta2), up.eps = (float)args->eps;
             up.factors = (const float*)args->scratch;
-            if (args->skip_zero_grad) nr_launch(k_adam_update<true>, dim3((unsigned)blocks), dim3(AD_BLOCK), 0, st, up);
-            else nr_launch(k_adam_update<false>, dim3((unsigned)blocks), dim3(AD_BLOCK), 0, st, up);
+            nr_launch(args->skip_zero_grad ? k_adam_update<true> : k_adam_update<false>, dim3((unsigned)blocks), dim3(AD_BLOCK), 0, st, up);
             int e = check_launch("k_adam_update");
             if (e) return e;
         }
@@ -1387,7 +1324,7 @@ static int validate_attributes(const NrAttributeArgs* a) {
     if (a->batch_size < 0 || a->num_faces < 0 || a->num_vertices < 0 || a->num_attributes < 0 || a->image_size <= 0)
         return fail(NR_ERR_ARGS, "bad sizes B=%d F=%d V=%d Va=%d s=%d", a->batch_size, a->num_faces, a->num_vertices,
                     a->num_attributes, a->image_size);
-    if (a->image_size > 16384 || (a->anti_aliasing ? 2 * a->image_size : a->image_size) > 16384)
+    if (a->image_size > 16384 || internal_size(a->anti_aliasing, a->image_size) > 16384)
         return fail(NR_ERR_ARGS, "image too large (s=%d)", a->image_size);
     if (a->num_channels < 1 || a->num_channels > NR_ATTR_MAX_CHANNELS)
         return fail(NR_ERR_ARGS, "bad channel count %d (1 .. %d)", a->num_channels, (int)NR_ATTR_MAX_CHANNELS);
@@ -1411,16 +1348,14 @@ int nr_attributes_forward(const NrAttributeArgs* a, float* images, void* stream)
     if (a->batch_size == 0) return NR_OK;
     if (!images) return fail(NR_ERR_ARGS, "null images");
     hipStream_t st = (hipStream_t)stream;
-    const int s = a->image_size, S = a->anti_aliasing ? 2 * s : s, C = a->num_channels;
+    const int s = a->image_size, S = internal_size(a->anti_aliasing, s), C = a->num_channels;
     if (attributes_empty(a)) {  // nothing drawn: background everywhere
-        if (hipMemsetAsync(images, 0, (size_t)a->batch_size * C * s * s * 4, st) != hipSuccess ||
-            (a->internal && hipMemsetAsync(a->internal, 0, (size_t)a->batch_size * S * S * C * 4, st) != hipSuccess))
-            return check_launch("hipMemsetAsync");
+        if (!zero_async(images, (size_t)a->batch_size * C * s * s * 4, st, &e)) return e;
+        if (a->internal && !zero_async(a->internal, (size_t)a->batch_size * S * S * C * 4, st, &e)) return e;
         return NR_OK;
     }
-    const dim3 grid((unsigned)(((long long)s * s + AT_BLOCK - 1) / AT_BLOCK), (unsigned)a->batch_size);
-    if (a->anti_aliasing) nr_launch(k_attr_fwd<true>, grid, dim3(AT_BLOCK), 0, st, *a, S, images);
-    else nr_launch(k_attr_fwd<false>, grid, dim3(AT_BLOCK), 0, st, *a, S, images);
+    nr_launch(a->anti_aliasing ? k_attr_fwd<true> : k_attr_fwd<false>, grid_1d((long long)s * s, AT_BLOCK, a->batch_size),
+              dim3(AT_BLOCK), 0, st, *a, S, images);
     return check_launch("k_attr_fwd");
 }
 
@@ -1439,9 +1374,8 @@ int nr_attributes_backward(const NrAttributeArgs* a, const float* grad_images, f
     const int Ba = a->attr_batch_stride ? B : 1;
     const size_t nv = (size_t)B * V * 3, na = (size_t)Ba * Va * C;
     if (attributes_empty(a)) {  // nothing drawn: zero gradients
-        if ((grad_vertices && nv && hipMemsetAsync(grad_vertices, 0, nv * 4, st) != hipSuccess) ||
-            (grad_attributes && na && hipMemsetAsync(grad_attributes, 0, na * 4, st) != hipSuccess))
-            return check_launch("hipMemsetAsync");
+        if (grad_vertices && nv && !zero_async(grad_vertices, nv * 4, st, &e)) return e;
+        if (grad_attributes && na && !zero_async(grad_attributes, na * 4, st, &e)) return e;
         return NR_OK;
     }
     if (!grad_vertices && !grad_attributes) return NR_OK;
@@ -1451,25 +1385,26 @@ int nr_attributes_backward(const NrAttributeArgs* a, const float* grad_images, f
     if (grad_attributes && (!attr_offsets || !attr_faces)) return fail(NR_ERR_ARGS, "grad_attributes needs the attribute CSR");
     const size_t need = nr_attributes_backward_workspace_bytes(B, F, C);
     if (!workspace || workspace_bytes < need) return fail(NR_ERR_WORKSPACE, "attribute backward workspace missing or too small");
-    if (hipMemsetAsync(workspace, 0, need, st) != hipSuccess) return check_launch("hipMemsetAsync");
+    if (!zero_async(workspace, need, st, &e)) return e;
     float* rec = (float*)workspace;
-    const int S = a->anti_aliasing ? 2 * a->image_size : a->image_size;
+    const int S = internal_size(a->anti_aliasing, a->image_size);
     const dim3 grid((unsigned)(((S + TW - 1) / TW) * ((S + TH - 1) / TH)), (unsigned)B);
-    if (grad_vertices && grad_attributes) nr_launch(k_attr_bwd<true, true>, grid, dim3(AT_BLOCK), 0, st, *a, S, grad_images, rec);
-    else if (grad_vertices) nr_launch(k_attr_bwd<true, false>, grid, dim3(AT_BLOCK), 0, st, *a, S, grad_images, rec);
-    else nr_launch(k_attr_bwd<false, true>, grid, dim3(AT_BLOCK), 0, st, *a, S, grad_images, rec);
+    auto kernel = k_attr_bwd<true, true>;  // <GV, GA>: at least one of the two is wanted here
+    if (!grad_attributes) kernel = k_attr_bwd<true, false>;
+    if (!grad_vertices) kernel = k_attr_bwd<false, true>;
+    nr_launch(kernel, grid, dim3(AT_BLOCK), 0, st, *a, S, grad_images, rec);
     e = check_launch("k_attr_bwd");
     if (e) return e;
     if (grad_vertices) {
         const long long n = (long long)B * V;
-        nr_launch(k_attr_vertex_sum, dim3((unsigned)((n + AT_BLOCK - 1) / AT_BLOCK)), dim3(AT_BLOCK), 0, st, (const float*)rec,
+        nr_launch(k_attr_vertex_sum, grid_1d(n, AT_BLOCK), dim3(AT_BLOCK), 0, st, (const float*)rec,
                   vertex_offsets, vertex_faces, grad_vertices, F, V, 3 + C, n);
         e = check_launch("k_attr_vertex_sum");
         if (e) return e;
     }
     if (grad_attributes) {
         const long long n = (long long)na;
-        nr_launch(k_attr_row_sum, dim3((unsigned)((n + AT_BLOCK - 1) / AT_BLOCK)), dim3(AT_BLOCK), 0, st, (const float*)rec,
+        nr_launch(k_attr_row_sum, grid_1d(n, AT_BLOCK), dim3(AT_BLOCK), 0, st, (const float*)rec,
                   attr_offsets, attr_faces, grad_attributes, B, F, Va, C, a->attr_batch_stride ? 0 : 1, n);
         e = check_launch("k_attr_row_sum");
     }
@@ -1479,7 +1414,7 @@ int nr_attributes_backward(const NrAttributeArgs* a, const float* grad_images, f
 int nr_selftest_division(const float* a, const float* b, float* q_fast, float* q_ieee, long long n, void* stream) {
     if (n < 0 || (n > 0 && (!a || !b || !q_fast || !q_ieee))) return fail(NR_ERR_ARGS, "bad arguments");
     if (n == 0) return NR_OK;
-    nr_launch(k_selftest_div, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a, b,
+    nr_launch(k_selftest_div, grid_1d(n, 256), dim3(256), 0, (hipStream_t)stream, a, b,
                        q_fast, q_ieee, n);
     return check_launch("k_selftest_div");
 }

@@ -104,6 +104,14 @@ def test_library_exports_every_header_symbol():
     L = ctypes.CDLL(_lib.LIB_PATH)
     for name in declared:
         assert hasattr(L, name), name
+    # the binding gives every symbol its argument types, and the return type the header declares
+    returns_size_t = set(re.findall(r"^\s*(?:NR_API\s+)?size_t\s+(nr_\w+)\s*\(", header, re.M))
+    assert returns_size_t == {name for name in declared if name.endswith(("_bytes", "_size"))}  # the regex missed none
+    for name in _lib.EXPORTS:
+        fn = getattr(_lib.lib(), name)
+        assert fn.argtypes is not None, name
+        want = ctypes.c_size_t if name in returns_size_t else ctypes.c_char_p if name == "nr_last_error" else ctypes.c_int
+        assert fn.restype is want, (name, fn.restype)
     assert _lib.lib().nr_version() == _lib.ABI_VERSION == 6
     assert _lib.lib().nr_hot_acc_bytes(0) == 0
     assert _lib.lib().nr_hot_acc_bytes(3) >= _lib.NR_HOT_COPIES * 3 * 64 * 4 + 3 * 8
