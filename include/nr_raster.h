@@ -627,6 +627,15 @@ enum { NR_LAUNCH_FUSED_SHADE = 1, NR_LAUNCH_STATIC_CHANNELS = 2, NR_LAUNCH_TWO_P
        NR_LAUNCH_SPLIT_FACES = 8192 };
 NR_API int nr_last_launch(const char* kernel, int* block_threads, int* flags);
 
+/* Dispatch order of a raster launch's tiles (no reference counterpart; host only, for tests and the
+ * timing tools).  With the items interleaved in groups (a batch that is a multiple of 8) the raster
+ * kernels hand out an item's nx x ny tiles of tile_w x tile_h pixels nearest the raster centre first:
+ * sorted by (dx^2 + dy^2, ty, tx) with dx = (2 tx + 1 - nx) tile_w and dy = (2 ty + 1 - ny) tile_h,
+ * in integers.  out[t] = tx | ty << 8 of rank t, nx * ny entries (k_raster_fwd: 32 x 32 bins;
+ * k_raster_bwd: 32 x 16 tiles).  NR_ERR_ARGS above 1024 tiles or 256 tiles a side: such a raster keeps
+ * the arithmetic order, rows from the middle row outwards and each row from its middle outwards. */
+NR_API int nr_tile_order(int nx, int ny, int tile_w, int tile_h, uint16_t* out);
+
 #ifdef NR_COUNT_TESTS
 /* Face-test counters, in the diagnostic build compiled with -DNR_COUNT_TESTS only
  * (_lib/libnr_raster_count.so, bench.py's face-test rate; SURVEY 8d's secondary bound, the reference's

@@ -131,6 +131,7 @@ SIGNATURES = {
     "nr_camera_workspace_bytes": (c_size_t, [c_int]),
     "nr_texture_packed_bytes": (c_size_t, [c_int, c_int, c_int]),
     "nr_last_launch": (c_int, [ctypes.c_char_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "nr_tile_order": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_uint16)]),
     "nr_hot_acc_bytes": (c_size_t, [c_int]),
     "nr_projection_args_size": (c_size_t, []),
     "nr_projection_forward": (c_int, [_args(NrProjectionArgs), _P, _P]),

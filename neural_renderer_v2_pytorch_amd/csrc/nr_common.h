@@ -129,6 +129,7 @@ struct Geom {
     int S, nbx, nby, nbins, nwords, tiles_x, tiles_y;
     int group;  // item-interleave group of the raster launches (block_item_tile); 0: per-item bands
     int B;      // items (the ordered forward's lists; set by run_face_index)
+    int table;  // the forward launch's TileOrder holds its bin order (block_item_tile); 0: the arithmetic order
 };
 
 Geom make_geom(int F, int S) {
@@ -142,8 +143,18 @@ Geom make_geom(int F, int S) {
     g.tiles_y = (S + TH - 1) / TH;
     g.group = 0;
     g.B = 0;
+    g.table = 0;
     return g;
 }
+
+// The bin order of an interleaved forward launch (block_item_tile, G > 0): rank t -> bin, nearest the
+// raster centre first (tile_order in nr_host.h builds it).  Passed by value beside Geom: a block reads
+// its entry from the kernel-argument segment through the scalar cache, one scalar load with no global
+// round trip before it, and a captured graph bakes the table in like every other argument.
+constexpr int TILE_ORDER_MAX = 1024;  // entries (2 KB); a raster of more tiles keeps the arithmetic centre_out order
+struct TileOrder {
+    uint32_t w[TILE_ORDER_MAX / 2];  // entry t: bits 16 (t & 1) .. + 15 of w[t >> 1] = tx | ty << 8
+};  // (whether a launch has one is Geom.table: read with the geometry, no load of its own)
 
 size_t align_up(size_t x) { return (x + 255) & ~size_t(255); }
 
@@ -681,8 +692,8 @@ __device__ __forceinline__ void xcd_tile(int L, int b, int nx, int ny, int& tx, 
 // the linear block id L = blockIdx.y gridDim.x + blockIdx.x (the dispatch order) runs over groups of
 // G items, and within a group over the tiles in row-major order with the item fastest (item = group
 // G + L % G).  Workgroups go to XCD L % 8 = item % 8, so an XCD keeps its items' face records in its
-// own L2.  The tiles run centre-out: rows from the middle row outwards, and each row's tiles from its
-// middle outwards, so a centred object's foreground tiles (whose waves live ~7x longer than a
+// own L2.  The tiles run centre-out (the forward's bins by its table instead, below): rows from the
+// middle row outwards, and each row's tiles from its middle outwards, so a centred object's foreground tiles (whose waves live ~7x longer than a
 // background tile's) start first and the kernel ends on the border rows' background tiles instead of
 // a tail of foreground tiles that started late (row-major order: headline fwd 0.148 -> 0.141 ms, the
 // backward unchanged; same-box A/B).  Smaller groups put fewer items on the same tile at once, which
@@ -692,14 +703,19 @@ __device__ __forceinline__ int centre_out(int k, int n) {
     return (n >> 1) + ((k & 1) ? -d : d);
 }
 // the interleaved order's coordinates of this block (G > 0): group, item within the group, and the
-// tile's position (kx, ky) in the centre-out order.  With L = blockIdx.y gridDim.x + blockIdx.x and
-// G gridDim.x blocks per group, the group is L / (G gridDim.x) = blockIdx.y / G (blockIdx.x <
-// gridDim.x) and r = L mod (G gridDim.x) is the remainder below.
-__device__ __forceinline__ void group_coords(int G, int nx, int& grp, int& item, int& kx, int& ky) {
+// tile's rank t in the group's order.  With L = blockIdx.y gridDim.x + blockIdx.x and G gridDim.x
+// blocks per group, the group is L / (G gridDim.x) = blockIdx.y / G (blockIdx.x < gridDim.x) and r =
+// L mod (G gridDim.x) is the remainder below; the item runs fastest within a rank.
+__device__ __forceinline__ void group_rank(int G, int& grp, int& item, int& t) {
     grp = udiv_uniform(blockIdx.y, G);
     const int r = (blockIdx.y - grp * G) * gridDim.x + blockIdx.x;
-    const int t = udiv_uniform(r, G);
+    t = udiv_uniform(r, G);
     item = r - t * G;
+}
+// ... and the tile's position (kx, ky) in the centre-out order
+__device__ __forceinline__ void group_coords(int G, int nx, int& grp, int& item, int& kx, int& ky) {
+    int t;
+    group_rank(G, grp, item, t);
     ky = udiv_uniform(t, nx);
     kx = t - ky * nx;
 }
@@ -709,6 +725,37 @@ __device__ __forceinline__ void block_item_tile(int G, int nx, int ny, int& b, i
         group_coords(G, nx, grp, item, kx, ky);
         b = grp * G + item;
         tx = centre_out(kx, nx);
+        ty = centre_out(ky, ny);
+        return;
+    }
+    b = blockIdx.y;
+    xcd_tile(blockIdx.x, b, nx, ny, tx, ty);
+}
+// The forward's map: with a table (Geom.table: ord holds one) an interleaved group's bins run by
+// distance from the raster centre instead: rank t's bin is entry t of the table, one scalar load from
+// the kernel arguments in place of the t / nx quotient and the two centre_out terms.  For a centred
+// object the foreground is a disc, and centre-out by rows dispatches the central rows' outer columns
+// (background) before the outer rows' central columns (foreground): on the headline the last bin of an
+// item with a candidate face has rank ~151 of 256 by rows and ~108 by distance, and the forward went
+// 0.1435 -> 0.1350 ms (same-box A/B, 3 runs each).  The backward keeps the rows: its tiles past the
+// foreground end at their bin flag after ~0.5 us, and the table gained it 0.3-0.6 % at a parent spread
+// of 1 % (DESIGN section 4 "Round 8"; tools/ablations/tile_order_bwd.patch).  Group 0 keeps xcd_tile.
+// (ord is the kernel's own by-value argument, indexed in place: the headline kernel sits at its 64-VGPR
+// budget without scratch, and handing the table on as a pointer that may be null measured 1.9 ms)
+__device__ __forceinline__ void block_item_tile(int G, int nx, int ny, bool table, const TileOrder& ord, int& b, int& tx,
+                                                int& ty) {
+    if (G > 0) {
+        int grp, item, t;
+        group_rank(G, grp, item, t);
+        b = grp * G + item;
+        if (table) {
+            const uint32_t e = ord.w[t >> 1] >> ((t & 1) * 16);
+            tx = e & 0xff;
+            ty = (e >> 8) & 0xff;
+            return;
+        }
+        const int ky = udiv_uniform(t, nx);
+        tx = centre_out(t - ky * nx, nx);
         ty = centre_out(ky, ny);
         return;
     }

@@ -854,7 +854,7 @@ __global__ __launch_bounds__(NTF) __attribute__((amdgpu_waves_per_eu(FWD_WPE, 8)
                                                   float* __restrict__ halo, uint8_t* __restrict__ binfg,
                                                   const int* __restrict__ order, int fim_sparse,
                                                   const int* __restrict__ split, int part,
-                                                  const uint8_t* __restrict__ sg_parts) {
+                                                  const uint8_t* __restrict__ sg_parts, TileOrder ord) {
     using C = FwdCfg<NTF>;
     static_assert(!SHADE || ((NTF == 256 || NTF == 1024) && COARSE == 32), "fused shading: threads 0-255 shade a pixel each");
     constexpr int NSUB = C::NSUB, FCAP = C::FCAP, CAND = C::CAND;
@@ -881,7 +881,7 @@ __global__ __launch_bounds__(NTF) __attribute__((amdgpu_waves_per_eu(FWD_WPE, 8)
         if (ob < 0) return;  // past this launch's part of the list (block-uniform, before any barrier)
         known_empty = ob == 1;
     } else {
-        block_item_tile(g.group, g.nbx, g.nby, b, bin_x, bin_y);
+        block_item_tile(g.group, g.nbx, g.nby, g.table != 0, ord, b, bin_x, bin_y);
     }
     const int bin = bin_y * g.nbx + bin_x;
     const int bx0 = bin_x * COARSE;

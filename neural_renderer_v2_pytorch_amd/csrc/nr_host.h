@@ -22,6 +22,55 @@ bool zero_async(void* p, size_t bytes, hipStream_t st, int* e) {
     return false;
 }
 
+// ---- tile order of the interleaved forward launch (TileOrder, block_item_tile) ----
+// The nx x ny tiles of tile_w x tile_h pixels by squared pixel distance of the tile's centre from the
+// raster's centre, ties by row, then column: an integer sort of (dx^2 + dy^2, ty, tx), dx = (2 tx + 1
+// - nx) tile_w and dy = (2 ty + 1 - ny) tile_h (twice the distance; pixels, so tiles that are not
+// square order correctly).  out: nx ny entries tx | ty << 8.  False when the raster has more
+// than TILE_ORDER_MAX tiles or a coordinate does not fit its 8 bits.
+bool tile_order_entries(int nx, int ny, int tile_w, int tile_h, uint16_t* out) {
+    if (nx < 1 || ny < 1 || tile_w < 1 || tile_h < 1 || nx > 256 || ny > 256 || nx * ny > TILE_ORDER_MAX) return false;
+    struct Key {
+        long long d2;
+        int ty, tx;
+    };
+    std::vector<Key> keys;
+    keys.reserve((size_t)nx * ny);
+    for (int ty = 0; ty < ny; ty++) {
+        for (int tx = 0; tx < nx; tx++) {
+            const long long dx = (long long)(2 * tx + 1 - nx) * tile_w, dy = (long long)(2 * ty + 1 - ny) * tile_h;
+            keys.push_back(Key{dx * dx + dy * dy, ty, tx});
+        }
+    }
+    std::sort(keys.begin(), keys.end(), [](const Key& a, const Key& b) {
+        return a.d2 != b.d2 ? a.d2 < b.d2 : (a.ty != b.ty ? a.ty < b.ty : a.tx < b.tx);
+    });
+    for (size_t t = 0; t < keys.size(); t++) out[t] = (uint16_t)(keys[t].tx | (keys[t].ty << 8));
+    return true;
+}
+// The table of a launch over nx x ny tiles: built once per geometry and kept for the life of the
+// process (a handful of rasters; map nodes do not move).  Sets g.table.  wanted = false (group 0, the
+// ordered forward) and rasters past the cap get an empty table and
+// g.table = 0: the arithmetic order.
+const TileOrder& tile_order(bool wanted, Geom& g, int nx, int ny, int tile_w, int tile_h) {
+    static const TileOrder none{};
+    g.table = 0;
+    if (!wanted || nx > 256 || ny > 256 || nx * ny > TILE_ORDER_MAX) return none;
+    static std::mutex mu;
+    static std::map<std::array<int, 4>, TileOrder> cache;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = cache.find({nx, ny, tile_w, tile_h});
+    if (it == cache.end()) {
+        TileOrder o{};
+        uint16_t e[TILE_ORDER_MAX];
+        if (!tile_order_entries(nx, ny, tile_w, tile_h, e)) return none;
+        for (int t = 0; t < nx * ny; t++) o.w[t >> 1] |= (uint32_t)e[t] << ((t & 1) * 16);
+        it = cache.emplace(std::array<int, 4>{nx, ny, tile_w, tile_h}, o).first;
+    }
+    g.table = 1;
+    return it->second;
+}
+
 // ---- workspace layouts ----
 // A workspace is cut once: every piece starts where the one before it ended, rounded up to 256 bytes.
 // Each *_layout below lists its pieces' byte offsets in order, then the total (a braced list is evaluated

@@ -38,8 +38,13 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <array>
 #include <cstdlib>
+#include <map>
+#include <mutex>
 #include <string>
+#include <vector>
 
 #include "nr_raster.h"
 
@@ -80,6 +85,14 @@ extern "C" {
 const char* nr_last_error(void) { return g_err.c_str(); }
 int nr_version(void) { return NR_ABI_VERSION; }
 size_t nr_raster_args_size(void) { return sizeof(NrRasterArgs); }
+
+int nr_tile_order(int nx, int ny, int tile_w, int tile_h, uint16_t* out) {
+    if (!out) return fail(NR_ERR_ARGS, "nr_tile_order: null output");
+    if (!tile_order_entries(nx, ny, tile_w, tile_h, out))
+        return fail(NR_ERR_ARGS, "nr_tile_order: %d x %d tiles of %d x %d pixels (1 to %d tiles, at most 256 a side)", nx, ny,
+                    tile_w, tile_h, TILE_ORDER_MAX);
+    return NR_OK;
+}
 
 int nr_num_channels(int draw_flags) {
     return ((draw_flags & NR_DRAW_RGB) ? 3 : 0) + ((draw_flags & NR_DRAW_SILHOUETTES) ? 1 : 0) +
@@ -330,10 +343,12 @@ static int run_face_index(const float* vertices, const int32_t* faces_idx, float
     const dim3 fwd_grid = side ? dim3(8 * deep_cap)
                           : qs ? dim3((unsigned)((long long)g.nbins * B + 3 * QS_CAP * lists)) : bins;
     const int rs = vertices ? FACE_REC : 9;
+    // the interleaved map's tile order (block_item_tile); the ordered forward reads its own lists
+    const TileOrder& ord = tile_order(!order && g.group > 0, g, g.nbx, g.nby, COARSE, COARSE);
     const auto launch = [&](const FwdVariant& v, dim3 grid, hipStream_t s) {
         nr_launch(raster_fwd_kernel(v), grid, dim3(v.ntf), 0, s, face_records, rs, bbox, mask, F, g, near, far, delta,
                   fim, sh, v.shade ? images : nullptr, v.shade ? ra->halo : nullptr, binfg, order, sparse, split_cnt,
-                  v.part, sg ? bin_part : nullptr);
+                  v.part, sg ? bin_part : nullptr, ord);
         return check_launch("k_raster_fwd");
     };
     g_last_fwd.store(LaunchRec{fwd.ntf, (fwd.shade ? NR_LAUNCH_FUSED_SHADE : 0) | (fwd.cc ? NR_LAUNCH_STATIC_CHANNELS : 0) |
