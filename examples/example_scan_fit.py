@@ -7,14 +7,17 @@ the loss carries sampling noise of the order of the sample spacing.  Here
 
   scan -> mesh   nr.PointMeshLoss(target): the squared distance from every scan point to its closest point
                  on its closest triangle, with the gradient to that triangle's corners: no sampling, no noise;
-  mesh -> scan   as before: fresh area-weighted samples of the current mesh (nr.sample_points, with the
-                 gradient back to the vertices) and nr.chamfer_distance(..., directions="x_to_y") to the scan,
-                 which keeps the mesh from growing surface where the scan has no points;
+  mesh -> scan   keeps the mesh from growing surface where the scan has no points.  --mesh-to-scan sampled (the
+                 default), as before: fresh area-weighted samples of the current mesh (nr.sample_points, with
+                 the gradient back to the vertices) and nr.chamfer_distance(..., directions="x_to_y") to the
+                 scan.  --mesh-to-scan exact: nr.MeshPointLoss(target), the squared distance from every
+                 triangle to its nearest scan point: no samples are drawn, and the whole scan loss is exact;
 
 plus a small nr.laplacian_loss that keeps the surface smooth, stepped by nr.Adam: every operation of the
 step is a fused HIP kernel.
 
-    python examples/example_scan_fit.py [--iters 300] [--samples 5000] [--level 3] [--out fitted.obj]
+    python examples/example_scan_fit.py [--iters 300] [--samples 5000] [--level 3] [--mesh-to-scan sampled|exact]
+                                        [--out fitted.obj]
 
 The target mesh defaults to tests/data/teapot.obj.
 """
@@ -32,7 +35,7 @@ DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests', '
 
 
 class ScanFit(torch.nn.Module):
-    def __init__(self, obj_file, level, samples, smoothness, device, seed=0):
+    def __init__(self, obj_file, level, samples, smoothness, device, seed=0, mesh_to_scan='sampled'):
         super().__init__()
         self.generator = torch.Generator(device=device).manual_seed(seed)
         vertices, faces = nr.load_obj(obj_file)
@@ -41,7 +44,8 @@ class ScanFit(torch.nn.Module):
             target = nr.sample_points(target_vertices, torch.as_tensor(faces).to(device).int(), samples,
                                       generator=self.generator)
         self.scan_to_mesh = nr.PointMeshLoss(target)
-        self.mesh_to_scan = nr.ChamferLoss(target, directions="x_to_y")
+        self.exact = mesh_to_scan == 'exact'
+        self.mesh_to_scan = nr.MeshPointLoss(target) if self.exact else nr.ChamferLoss(target, directions="x_to_y")
         sphere, sphere_faces = synthetic.icosphere(level, radius=0.5)
         self.faces = torch.as_tensor(sphere_faces).to(device).int()
         self.vertices = torch.nn.Parameter(torch.as_tensor(sphere).float().to(device))
@@ -49,12 +53,15 @@ class ScanFit(torch.nn.Module):
         self.samples, self.smoothness = samples, smoothness
 
     def forward(self):
+        if self.exact:
+            return (self.scan_to_mesh(self.vertices, self.faces), self.mesh_to_scan(self.vertices, self.faces),
+                    nr.laplacian_loss(self.vertices, self.topology))
         points = nr.sample_points(self.vertices, self.faces, self.samples, generator=self.generator)
         return (self.scan_to_mesh(self.vertices, self.faces), self.mesh_to_scan(points),
                 nr.laplacian_loss(self.vertices, self.topology))
 
 
-def main():
+def parser():
     ap = argparse.ArgumentParser()
     ap.add_argument('--obj', default=os.path.join(DATA, 'teapot.obj'))
     ap.add_argument('--iters', type=int, default=300)
@@ -62,9 +69,16 @@ def main():
     ap.add_argument('--level', type=int, default=3, help='icosphere subdivision level')
     ap.add_argument('--smoothness', type=float, default=0.01, help='weight of the Laplacian loss')
     ap.add_argument('--gpu', type=int, default=0)
+    ap.add_argument('--mesh-to-scan', choices=('sampled', 'exact'), default='sampled',
+                    help="the mesh -> scan term: fresh surface samples and a one-sided chamfer term, or nr.MeshPointLoss")
     ap.add_argument('--out', default=None, help='write the fitted mesh as an .obj file')
-    args = ap.parse_args()
-    model = ScanFit(args.obj, args.level, args.samples, args.smoothness, torch.device('cuda', args.gpu))
+    return ap
+
+
+def main():
+    args = parser().parse_args()
+    model = ScanFit(args.obj, args.level, args.samples, args.smoothness, torch.device('cuda', args.gpu),
+                    mesh_to_scan=args.mesh_to_scan)
     opt = nr.Adam(model.parameters(), lr=0.01)
     history = []
     for _ in range(args.iters):

@@ -592,6 +592,48 @@ NR_API int nr_point_mesh_backward(const float* points, long long points_batch_st
                                   const float* grad_loss, int batch_size, int num_points, int num_vertices,
                                   int num_faces, float* grad_points, float* grad_vertices, void* stream);
 
+/* Face-to-scan distance (point_loss.py mesh_point_distance / closest_points_to_faces; no reference
+ * counterpart): the opposite direction of the point-to-surface distance above, with the same arguments:
+ * points [B, N, 3] with the item stride points_batch_stride in elements (0: one [N, 3] set shared by every
+ * item, read in place), vertices [B, V, 3] contiguous, faces [F, 3] (trusted: below V).  With T_f the
+ * triangle f as a closed set:
+ *   point[b, f]   = argmin_i dist^2(p_i, T_f), the lowest i among exact float32 ties
+ *   weights[b, f] = the barycentric weights of the closest point c_f of T_f to p_point[b, f]
+ *   dist2[b, f]   = |p_point[b, f] - c_f|^2
+ *   loss_b        = (1/F) sum_f dist2[b, f]   (one fixed order)
+ * Every face counts.  The point is chosen by the float32 pair distance of the point-to-surface loop (the
+ * same operations in the same order); the closest point on the face is then formed in float64 from the
+ * float32 inputs, and its weights and squared distance are rounded to float32 once.  Degenerate faces follow
+ * the rules stated above (a segment between the two most distant corners, or a point).
+ * Backward, point and weights held constant:
+ *   grad v_j = -g_b (2/F) sum over (f, k) with faces[f, k] == j of w_fk (p_point(f) - c_f)
+ *   grad p_i =  g_b (2/F) sum over f with point(f) == i of (p_i - c_f)
+ * corner_offsets [V + 1] and corner_index [3 F] are the CSR lists vertex -> its corners 3 f + k, ascending
+ * (trusted); grad_vertices is gathered over them in that order without atomics.  dist2, point, weights,
+ * loss and grad_vertices are bitwise reproducible (every sum in one fixed order, the same whether or not the
+ * points were split over several blocks); grad_points is scattered with float atomics (many faces share a
+ * nearest point) and agrees from run to run up to the order of float additions.
+ * Checked before any launch (NR_ERR_ARGS, also for a missing or short workspace): N, F, V >= 1,
+ * B <= 65535, B * F <= INT_MAX - 4096, B * N and 3 B V <= INT_MAX, a non-negative stride, non-null inputs, at
+ * least one output.  With B == 0 nothing is launched (the sizes are checked first: B == 0 with N, F or V
+ * below 1 is still NR_ERR_ARGS, as in the point-to-surface calls).  The saved point indices are inside [0, N)
+ * whatever the coordinates hold (NaN included). */
+NR_API size_t nr_face_point_workspace_bytes(int batch_size, int num_points, int num_faces);
+/* dist2 [B, F], point [B, F], weights [B, F, 3], loss [B]: each may be NULL (not all four); each one given
+ * is fully written. */
+NR_API int nr_face_point_forward(const float* points, long long points_batch_stride, const float* vertices,
+                                 const int32_t* faces, int batch_size, int num_points, int num_vertices,
+                                 int num_faces, float* dist2, int32_t* point, float* weights, float* loss,
+                                 void* workspace, size_t workspace_bytes, void* stream);
+/* grad_loss [B] -> grad_points [B, N, 3] (dense, also for shared points; zero-filled by the call),
+ * grad_vertices [B, V, 3] (fully written, zeros for a vertex without a face); either may be NULL (the CSR
+ * lists are needed for grad_vertices only).  point and weights are the forward's (trusted). */
+NR_API int nr_face_point_backward(const float* points, long long points_batch_stride, const float* vertices,
+                                  const int32_t* faces, const int32_t* corner_offsets, const int32_t* corner_index,
+                                  const int32_t* point, const float* weights, const float* grad_loss,
+                                  int batch_size, int num_points, int num_vertices, int num_faces,
+                                  float* grad_points, float* grad_vertices, void* stream);
+
 /* Diagnostics (no reference counterpart): the kernels replace some IEEE divisions by a shortened
  * form of the compiler's own division sequence inside a guarded operand range (DESIGN.md,
  * "Numerics").  This runs both forms on n operand pairs so tests can check they agree bit for bit. */
@@ -609,7 +651,7 @@ NR_API int nr_profile_enable(int on);
 NR_API int nr_profile_read(const char* kernel, float* ms);
 
 /* Launch record (no reference counterpart; the tests use it to assert which kernel variant ran).
- * For the most recent launch of `kernel` ("k_raster_fwd", "k_raster_bwd", or "k_chamfer_nn" / "k_point_face_nn": 256 threads) in this process
+ * For the most recent launch of `kernel` ("k_raster_fwd", "k_raster_bwd", or "k_chamfer_nn" / "k_point_face_nn" / "k_face_point_nn": 256 threads) in this process
  * (process-wide, like the profiling hook; torch issues a backward from its autograd thread): block_threads = threads per block (k_raster_fwd: 256 = four 16x16 quadrants per
  * 32x32 bin, 1024 = one wave per 8x8 block; k_raster_bwd: 256 = 2 pixels per lane, 512 = 1 pixel
  * per lane) and flags = NR_LAUNCH_* bits.  NR_ERR_ARGS when none was recorded. */
@@ -624,7 +666,9 @@ enum { NR_LAUNCH_FUSED_SHADE = 1, NR_LAUNCH_STATIC_CHANNELS = 2, NR_LAUNCH_TWO_P
        /* k_chamfer_nn: the direction's targets were split over several blocks and combined */
        NR_LAUNCH_SPLIT_X_TO_Y = 2048, NR_LAUNCH_SPLIT_Y_TO_X = 4096,
        /* k_point_face_nn: the faces were split over several blocks and combined */
-       NR_LAUNCH_SPLIT_FACES = 8192 };
+       NR_LAUNCH_SPLIT_FACES = 8192,
+       /* k_face_point_nn: the points were split over several blocks and combined */
+       NR_LAUNCH_SPLIT_POINTS = 16384 };
 NR_API int nr_last_launch(const char* kernel, int* block_threads, int* flags);
 
 /* Dispatch order of a raster launch's tiles (no reference counterpart; host only, for tests and the

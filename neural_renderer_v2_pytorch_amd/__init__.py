@@ -24,8 +24,10 @@ from .image_loss import (HuberLoss, IoULoss, SquaredErrorLoss, huber_loss, huber
 from .optimizers import Adam, adam_step_torch
 from .attributes import (NR_ATTR_MAX_CHANNELS, attributes_from_maps_torch, rasterize_attributes,
                          rasterize_attributes_torch)
-from .point_loss import (ChamferLoss, PointMeshLoss, chamfer_distance, chamfer_distance_torch, closest_points_on_mesh,
-                         closest_points_on_mesh_torch, nearest_points, nearest_points_torch, point_mesh_distance,
-                         point_mesh_distance_torch, sample_points, sample_points_torch)
+from .point_loss import (ChamferLoss, MeshPointLoss, PointMeshLoss, chamfer_distance, chamfer_distance_torch,
+                         closest_points_on_mesh, closest_points_on_mesh_torch, closest_points_to_faces,
+                         closest_points_to_faces_torch, mesh_point_distance, mesh_point_distance_torch, nearest_points,
+                         nearest_points_torch, point_mesh_distance, point_mesh_distance_torch, sample_points,
+                         sample_points_torch)
 
 __version__ = '2.0.2+mi355x.1'

@@ -24,6 +24,7 @@ NR_LAUNCH_HOT_WINDOWS, NR_LAUNCH_DEALT_QUARTERS, NR_LAUNCH_QUADRANTS = 32, 64, 1
 NR_LAUNCH_LIGHTS, NR_LAUNCH_BACKGROUNDS, NR_LAUNCH_SIL_ONLY = 256, 512, 1024  # k_raster_bwd's feature instantiation
 NR_LAUNCH_SPLIT_X_TO_Y, NR_LAUNCH_SPLIT_Y_TO_X = 2048, 4096  # k_chamfer_nn: a direction's targets split over several blocks
 NR_LAUNCH_SPLIT_FACES = 8192  # k_point_face_nn: the faces split over several blocks
+NR_LAUNCH_SPLIT_POINTS = 16384  # k_face_point_nn: the points split over several blocks
 NR_HOT_MAX, NR_HOT_COPIES = 256, 32
 
 c_int, c_float, c_void_p, c_size_t, c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong
@@ -59,6 +60,8 @@ NR_CHAMFER_X_TO_Y, NR_CHAMFER_Y_TO_X = 1, 2
 NR_CHAMFER_TILE = 1024  # csrc/nr_point_loss.h PL_TILE: targets staged in LDS at a time
 NR_POINT_MESH_TILE, NR_POINT_MESH_QBLOCK = 256, 1024  # csrc/nr_point_mesh.h PM_TILE (face records in LDS), PM_QBLOCK (queries per block)
 NR_POINT_MESH_SPLIT_BLOCKS = 4096  # PM_SPLIT_BLOCKS: the faces are split over further blocks while a launch has fewer
+NR_FACE_POINT_TILE, NR_FACE_POINT_FBLOCK = 64, 256  # csrc/nr_face_point.h FP_TILE (points in LDS), FP_FBLOCK (faces per block)
+NR_FACE_POINT_SPLIT_BLOCKS = 4096  # FP_SPLIT_BLOCKS: the points are split over further blocks while a launch has fewer
 
 
 class NrCameraArgs(ctypes.Structure):  # include/nr_raster.h
@@ -163,6 +166,9 @@ SIGNATURES = {
     "nr_point_mesh_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "nr_point_mesh_forward": (c_int, [_P, c_ll, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "nr_point_mesh_backward": (c_int, [_P, c_ll, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "nr_face_point_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "nr_face_point_forward": (c_int, [_P, c_ll, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "nr_face_point_backward": (c_int, [_P, c_ll, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -181,7 +187,7 @@ def lib():
         raise RuntimeError("neural_renderer_v2_pytorch_amd: HIP library %s is missing; build it with "
                            "__graft_entry__.build() (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_adam_*, nr_attributes_*, point-loss and nr_point_mesh_* entry points): a library built before them
+    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_adam_*, nr_attributes_*, point-loss, nr_point_mesh_* and nr_face_point_* entry points): a library built before them
     # still reports the version this binding expects
     missing = [name for name in EXPORTS if not hasattr(L, name)]
     if missing:
@@ -206,7 +212,7 @@ def lib():
 
 def last_launch(kernel):
     """(threads per block, NR_LAUNCH_* flags) of the latest launch of `kernel` ("k_raster_fwd",
-    "k_raster_bwd", "k_chamfer_nn" or "k_point_face_nn") in this process: the variant the library actually ran."""
+    "k_raster_bwd", "k_chamfer_nn", "k_point_face_nn" or "k_face_point_nn") in this process: the variant the library actually ran."""
     t, f = c_int(), c_int()
     check(lib().nr_last_launch(kernel.encode(), ctypes.byref(t), ctypes.byref(f)), "nr_last_launch")
     return t.value, f.value

@@ -164,6 +164,20 @@ PointMeshLayout point_mesh_layout(int B, int N, int F) {
             c.take_if(p.nsplit > 1, part), c.off};
 }
 
+// face-to-scan: records [B, F, PM_REC], the nearest point [B, F], the loop's and the finish's dist2 [B, F] each,
+// and on the split path the partial d2 and i [B, nsplit, F] each (the faces are the queries, the points the targets)
+struct FacePointLayout {
+    SplitPlan plan;
+    size_t records, nearest, loop_d2, fin_d2, part_d2, part_i, total;
+};
+FacePointLayout face_point_layout(int B, int N, int F) {
+    const SplitPlan p = split_plan(B, F, N, FP_FBLOCK, FP_TILE, FP_SPLIT_BLOCKS);
+    const size_t bf = (size_t)B * F * 4, part = bf * p.nsplit;
+    Cutter c;
+    return {p, c.take((size_t)B * F * PM_REC * 4), c.take(bf), c.take(bf), c.take(bf), c.take_if(p.nsplit > 1, part),
+            c.take_if(p.nsplit > 1, part), c.off};
+}
+
 int validate_raster(const NrRasterArgs* a, bool need_workspace) {
     if (!a) return fail(NR_ERR_ARGS, "null args");
     if (a->batch_size < 0 || a->num_faces < 0 || a->num_vertices < 0 || a->image_size <= 0)

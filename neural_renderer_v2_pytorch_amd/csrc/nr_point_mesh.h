@@ -109,6 +109,25 @@ __device__ __forceinline__ float pm_segment(float rx, float ry, float rz, float 
     return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
 }
 
+// The float32 point-face test of both nearest-neighbour loops (k_point_face_nn here, k_face_point_nn in
+// nr_face_point.h): the squared distance from the point q to the face of one record (A .. NN its six
+// 16-byte pieces, bc = ac - ab in float32).  Branch-free: the least of the distances to the three edges and,
+// where the projection falls inside, to the plane.  One body, so the two directions choose by the same bits.
+__device__ __forceinline__ float pm_pair_dist2(float qx, float qy, float qz, const float4& A, const float4& AB, const float4& AC,
+                                               const float4& GV, const float4& GW, const float4& NN, float bcx, float bcy,
+                                               float bcz) {
+    const float px = qx - A.x, py = qy - A.y, pz = qz - A.z;
+    const float v = fmaf(pz, GV.z, fmaf(py, GV.y, px * GV.x));
+    const float w = fmaf(pz, GW.z, fmaf(py, GW.y, px * GW.x));
+    const float h = fmaf(pz, NN.z, fmaf(py, NN.y, px * NN.x));
+    const bool inside = (v >= 0.f) & (w >= 0.f) & (v + w <= GV.w);
+    const float plane = inside ? h * h : INFINITY;
+    const float e0 = pm_segment(px, py, pz, AB.x, AB.y, AB.z, A.w);
+    const float e1 = pm_segment(px, py, pz, AC.x, AC.y, AC.z, AB.w);
+    const float e2 = pm_segment(px - AB.x, py - AB.y, pz - AB.z, bcx, bcy, bcz, AC.w);
+    return fminf(fminf(e0, e1), fminf(e2, plane));
+}
+
 // One direction of work: for every query point its nearest face.
 struct PmArgs {
     const float* points;     // [B, N, 3], item stride p_stride (elements; 0 = shared)
@@ -163,16 +182,7 @@ __global__ __launch_bounds__(PL_BLOCK) void k_point_face_nn(PmArgs d) {
             const int f = f0 + e;
 #pragma unroll
             for (int k = 0; k < PM_Q; k++) {
-                const float px = qx[k] - A.x, py = qy[k] - A.y, pz = qz[k] - A.z;
-                const float v = fmaf(pz, GV.z, fmaf(py, GV.y, px * GV.x));
-                const float w = fmaf(pz, GW.z, fmaf(py, GW.y, px * GW.x));
-                const float h = fmaf(pz, NN.z, fmaf(py, NN.y, px * NN.x));
-                const bool inside = (v >= 0.f) & (w >= 0.f) & (v + w <= GV.w);
-                const float plane = inside ? h * h : INFINITY;
-                const float e0 = pm_segment(px, py, pz, AB.x, AB.y, AB.z, A.w);
-                const float e1 = pm_segment(px, py, pz, AC.x, AC.y, AC.z, AB.w);
-                const float e2 = pm_segment(px - AB.x, py - AB.y, pz - AB.z, bcx, bcy, bcz, AC.w);
-                const float d2 = fminf(fminf(e0, e1), fminf(e2, plane));
+                const float d2 = pm_pair_dist2(qx[k], qy[k], qz[k], A, AB, AC, GV, GW, NN, bcx, bcy, bcz);
                 const bool less = d2 < best[k];
                 best[k] = less ? d2 : best[k];
                 bf[k] = less ? f : bf[k];
@@ -200,29 +210,14 @@ __device__ __forceinline__ double pm_segment64(const double* r, const double* e,
     return dx * dx + dy * dy + dz * dz;
 }
 
-// One thread per point: the closest point on the winning face again, in float64 from the float32 corners
-// (the loop's float32 distance only chose the face), so that the weights are those of the closest point
-// to rounding, thin faces included.  weights = the barycentric weights over the face's corners, rounded
-// once; dist2 = |p - (w0 a + w1 b + w2 c)|^2, formed in float64 before the weights are rounded and
-// rounded once.  A regular face: the plane's closest point where it falls
-// inside, else the nearest of the three edges (ab, ac, bc in this order, the first among equals).  A
-// degenerate face (pm_degenerate): its longest edge in the same order, the third corner's weight 0; a
-// point (all corners equal) gives (1, 0, 0).  grid: (ceil(N / 256), B).
-__global__ __launch_bounds__(PL_BLOCK) void k_point_face_finish(const float* __restrict__ points, long long p_stride,
-                                                                const float* __restrict__ vertices, const int32_t* __restrict__ faces,
-                                                                const int32_t* __restrict__ nearest, int N, int V,
-                                                                float* __restrict__ dist2, int32_t* __restrict__ face,
-                                                                float* __restrict__ weights) {
-    const int i = blockIdx.x * PL_BLOCK + threadIdx.x, b = blockIdx.y;
-    if (i >= N) return;
-    const long long n = (long long)b * N + i;
-    const int f = nearest[n];
-    const float* p = points + (long long)b * p_stride + (long long)i * 3;
-    const float* vb = vertices + (long long)b * V * 3;
-    const int i0 = faces[3 * (long long)f], i1 = faces[3 * (long long)f + 1], i2 = faces[3 * (long long)f + 2];
-    const float* pa = vb + (long long)i0 * 3;
-    const float* pb = vb + (long long)i1 * 3;
-    const float* pc = vb + (long long)i2 * 3;
+// The float64 closest point of both finishes (k_point_face_finish here, k_face_point_finish in
+// nr_face_point.h): the closest point of the face (corners pa, pb, pc with the indices i0, i1, i2) to p, formed
+// in float64 from the float32 values.  w takes its barycentric weights (unrounded); returns |p - (w0 a + w1 b +
+// w2 c)|^2.  A regular face: the plane's closest point where it falls inside, else the nearest of the three
+// edges (ab, ac, bc in this order, the first among equals).  A degenerate face (pm_degenerate): its longest edge
+// in the same order, the third corner's weight 0; a point (all corners equal) gives (1, 0, 0).
+__device__ __forceinline__ double pm_closest64(const float* p, int i0, int i1, int i2, const float* pa, const float* pb,
+                                               const float* pc, double* wt) {
     double ab[3], ac[3], bc[3], ap[3], bp[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
@@ -250,9 +245,35 @@ __global__ __launch_bounds__(PL_BLOCK) void k_point_face_finish(const float* __r
     double dd[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) dd[k] = (double)p[k] - ((w0 * (double)pa[k] + w1 * (double)pb[k]) + w2 * (double)pc[k]);
-    if (dist2) dist2[n] = (float)((dd[0] * dd[0] + dd[1] * dd[1]) + dd[2] * dd[2]);
+    wt[0] = w0, wt[1] = w1, wt[2] = w2;
+    return (dd[0] * dd[0] + dd[1] * dd[1]) + dd[2] * dd[2];
+}
+
+// One thread per point: the closest point on the winning face again, in float64 from the float32 corners
+// (the loop's float32 distance only chose the face), so that the weights are those of the closest point
+// to rounding, thin faces included.  weights = the barycentric weights over the face's corners, rounded
+// once; dist2 = |p - (w0 a + w1 b + w2 c)|^2, formed in float64 before the weights are rounded and
+// rounded once (pm_closest64 has the rules).  grid: (ceil(N / 256), B).
+__global__ __launch_bounds__(PL_BLOCK) void k_point_face_finish(const float* __restrict__ points, long long p_stride,
+                                                                const float* __restrict__ vertices, const int32_t* __restrict__ faces,
+                                                                const int32_t* __restrict__ nearest, int N, int V,
+                                                                float* __restrict__ dist2, int32_t* __restrict__ face,
+                                                                float* __restrict__ weights) {
+    const int i = blockIdx.x * PL_BLOCK + threadIdx.x, b = blockIdx.y;
+    if (i >= N) return;
+    const long long n = (long long)b * N + i;
+    const int f = nearest[n];
+    const float* p = points + (long long)b * p_stride + (long long)i * 3;
+    const float* vb = vertices + (long long)b * V * 3;
+    const int i0 = faces[3 * (long long)f], i1 = faces[3 * (long long)f + 1], i2 = faces[3 * (long long)f + 2];
+    const float* pa = vb + (long long)i0 * 3;
+    const float* pb = vb + (long long)i1 * 3;
+    const float* pc = vb + (long long)i2 * 3;
+    double w[3];
+    const double d2 = pm_closest64(p, i0, i1, i2, pa, pb, pc, w);
+    if (dist2) dist2[n] = (float)d2;
     if (face) face[n] = f;
-    if (weights) weights[n * 3] = (float)w0, weights[n * 3 + 1] = (float)w1, weights[n * 3 + 2] = (float)w2;
+    if (weights) weights[n * 3] = (float)w[0], weights[n * 3 + 1] = (float)w[1], weights[n * 3 + 2] = (float)w[2];
 }
 
 // One thread per point: c = w0 a + w1 b + w2 c of the saved face and weights, d = p - c,

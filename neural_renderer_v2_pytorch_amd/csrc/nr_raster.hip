@@ -27,7 +27,7 @@
 // perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian and
 // flatten regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_adam.h
 // (multi-tensor Adam), nr_attributes.h (per-vertex attribute rendering), nr_point_loss.h (chamfer distance,
-// nearest points and surface sampling), nr_point_mesh.h (point-to-surface distance), nr_host.h (workspace layouts, launch helpers, argument checks); this file holds the extern "C" ABI.
+// nearest points and surface sampling), nr_point_mesh.h (point-to-surface distance), nr_face_point.h (face-to-scan distance), nr_host.h (workspace layouts, launch helpers, argument checks); this file holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -65,6 +65,7 @@
 #include "nr_attributes.h"
 #include "nr_point_loss.h"
 #include "nr_point_mesh.h"
+#include "nr_face_point.h"
 #include "nr_host.h"
 
 
@@ -1137,6 +1138,96 @@ int nr_point_mesh_backward(const float* points, long long points_batch_stride, c
     return check_launch("k_point_mesh_bwd");
 }
 
+// ---- face-to-scan distance (nr_face_point.h) ----
+static int validate_face_point(int B, int N, int V, int F) {
+    if (B < 0) return fail(NR_ERR_ARGS, "bad batch size B=%d", B);
+    if (N <= 0 || F <= 0 || V <= 0) return fail(NR_ERR_ARGS, "empty input N=%d F=%d V=%d (each must be at least 1)", N, F, V);
+    if (B > 65535) return fail(NR_ERR_ARGS, "too many items B=%d (at most 65535)", B);
+    if ((long long)B * F > INT_MAX - 4096 || (long long)B * N > INT_MAX || (long long)B * V > INT_MAX / 3)
+        return fail(NR_ERR_ARGS, "too many points, faces or vertices B=%d N=%d F=%d V=%d", B, N, F, V);
+    return NR_OK;
+}
+
+size_t nr_face_point_workspace_bytes(int batch_size, int num_points, int num_faces) {
+    if (batch_size <= 0 || num_points <= 0 || num_faces <= 0) return 0;
+    return face_point_layout(batch_size, num_points, num_faces).total;
+}
+
+int nr_face_point_forward(const float* points, long long points_batch_stride, const float* vertices, const int32_t* faces,
+                          int batch_size, int num_points, int num_vertices, int num_faces, float* dist2, int32_t* point,
+                          float* weights, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+    const int B = batch_size, N = num_points, V = num_vertices, F = num_faces;
+    int e = validate_face_point(B, N, V, F);
+    if (e) return e;
+    if (points_batch_stride < 0) return fail(NR_ERR_ARGS, "negative points batch stride");
+    if (B == 0) return NR_OK;
+    if (!points || !vertices || !faces) return fail(NR_ERR_ARGS, "null points, vertices or faces");
+    if (!dist2 && !point && !weights && !loss) return fail(NR_ERR_ARGS, "no output asked for");
+    if (!workspace || workspace_bytes < nr_face_point_workspace_bytes(B, N, F))
+        return fail(NR_ERR_ARGS, "face_point workspace missing or too small");
+    hipStream_t st = (hipStream_t)stream;
+    const FacePointLayout wl = face_point_layout(B, N, F);
+    const SplitPlan p = wl.plan;
+    char* ws = (char*)workspace;
+    float* records = (float*)(ws + wl.records);
+    int32_t* nearest = (int32_t*)(ws + wl.nearest);
+    float* loop_d2 = (float*)(ws + wl.loop_d2);
+    float* fin_d2 = dist2 ? dist2 : (float*)(ws + wl.fin_d2);
+    const dim3 per_face = grid_1d(F, PL_BLOCK, B);
+    nr_launch(k_point_face_records, per_face, dim3(PL_BLOCK), 0, st, vertices, faces, V, F, records);
+    e = check_launch("k_point_face_records");
+    if (e) return e;
+    FpArgs d;
+    d.points = points, d.p_stride = points_batch_stride, d.records = records, d.N = N, d.F = F, d.nsplit = p.nsplit;
+    if (p.nsplit > 1) {
+        d.dist2 = (float*)(ws + wl.part_d2), d.point = (int32_t*)(ws + wl.part_i);
+    } else {
+        d.dist2 = loop_d2, d.point = nearest;
+    }
+    nr_launch(k_face_point_nn, dim3((unsigned)(p.nqb * p.nsplit), (unsigned)B), dim3(PL_BLOCK), 0, st, d);
+    g_last_face_point.store(LaunchRec{PL_BLOCK, p.nsplit > 1 ? NR_LAUNCH_SPLIT_POINTS : 0});
+    e = check_launch("k_face_point_nn");
+    if (e) return e;
+    if (p.nsplit > 1) {
+        nr_launch(k_chamfer_combine, per_face, dim3(PL_BLOCK), 0, st, (const float*)d.dist2, (const int32_t*)d.point, F, p.nsplit,
+                  loop_d2, nearest);
+        e = check_launch("k_chamfer_combine");
+        if (e) return e;
+    }
+    const bool need_d2 = dist2 || loss;
+    nr_launch(k_face_point_finish, per_face, dim3(PL_BLOCK), 0, st, points, points_batch_stride, vertices, faces,
+              (const int32_t*)nearest, V, F, need_d2 ? fin_d2 : (float*)nullptr, point, weights);
+    e = check_launch("k_face_point_finish");
+    if (e || !loss) return e;
+    nr_launch(k_chamfer_sum, dim3((unsigned)B), dim3(PL_WIDE), 0, st, (const float*)fin_d2, F, (const float*)nullptr, 0, loss);
+    return check_launch("k_chamfer_sum");
+}
+
+int nr_face_point_backward(const float* points, long long points_batch_stride, const float* vertices, const int32_t* faces,
+                           const int32_t* corner_offsets, const int32_t* corner_index, const int32_t* point, const float* weights,
+                           const float* grad_loss, int batch_size, int num_points, int num_vertices, int num_faces,
+                           float* grad_points, float* grad_vertices, void* stream) {
+    const int B = batch_size, N = num_points, V = num_vertices, F = num_faces;
+    int e = validate_face_point(B, N, V, F);
+    if (e) return e;
+    if (points_batch_stride < 0) return fail(NR_ERR_ARGS, "negative points batch stride");
+    if (B == 0 || (!grad_points && !grad_vertices)) return NR_OK;
+    if (!points || !vertices || !faces || !point || !weights || !grad_loss) return fail(NR_ERR_ARGS, "null pointer");
+    if (grad_vertices && (!corner_offsets || !corner_index)) return fail(NR_ERR_ARGS, "grad_vertices needs the corner CSR lists");
+    hipStream_t st = (hipStream_t)stream;
+    if (grad_vertices) {
+        nr_launch(k_face_point_bwd_vertices, grid_1d(V, PL_BLOCK, B), dim3(PL_BLOCK), 0, st, points, points_batch_stride, vertices,
+                  faces, corner_offsets, corner_index, point, weights, grad_loss, V, F, grad_vertices);
+        e = check_launch("k_face_point_bwd_vertices");
+        if (e) return e;
+    }
+    if (!grad_points) return NR_OK;
+    if (!zero_async(grad_points, (size_t)B * N * 3 * 4, st, &e)) return e;
+    nr_launch(k_face_point_bwd_points, grid_1d(F, PL_BLOCK, B), dim3(PL_BLOCK), 0, st, points, points_batch_stride, vertices,
+              faces, point, weights, grad_loss, N, V, F, grad_points);
+    return check_launch("k_face_point_bwd_points");
+}
+
 // ---- image losses (nr_image_loss.h) ----
 static long long il_chunks(int n) { return ((long long)n + IL_CHUNK - 1) / IL_CHUNK; }
 
@@ -1465,7 +1556,8 @@ int nr_last_launch(const char* kernel, int* block_threads, int* flags) {
     const LaunchSlot* slot = strcmp(kernel, "k_raster_fwd") == 0 ? &g_last_fwd
                              : strcmp(kernel, "k_raster_bwd") == 0 ? &g_last_bwd
                              : strcmp(kernel, "k_chamfer_nn") == 0 ? &g_last_chamfer
-                             : strcmp(kernel, "k_point_face_nn") == 0 ? &g_last_point_mesh : nullptr;
+                             : strcmp(kernel, "k_point_face_nn") == 0 ? &g_last_point_mesh
+                             : strcmp(kernel, "k_face_point_nn") == 0 ? &g_last_face_point : nullptr;
     if (!slot) return fail(NR_ERR_ARGS, "nr_last_launch: unknown kernel name %s", kernel);
     const LaunchRec r = slot->load();
     if (!r.threads) return fail(NR_ERR_ARGS, "nr_last_launch: no %s launch recorded in this process", kernel);

@@ -1,9 +1,11 @@
 """3-D point supervision for the optimisation loop around the renderer: the chamfer distance between two
 point sets, the nearest-neighbour query under it, area-weighted sampling of points on a mesh, and the
-distance from a point set to the surface of a mesh.  Each is a fused HIP launch sequence (nr_chamfer_* /
-nr_sample_points_* / nr_point_mesh_*, include/nr_raster.h) for float32 GPU tensors and a torch composition
+distance from a point set to the surface of a mesh and from the faces of a mesh to a point set.  Each is a
+fused HIP launch sequence (nr_chamfer_* / nr_sample_points_* / nr_point_mesh_* / nr_face_point_*,
+include/nr_raster.h) for float32 GPU tensors and a torch composition
 (chamfer_distance_torch / nearest_points_torch / sample_points_torch / point_mesh_distance_torch /
-closest_points_on_mesh_torch) for every other device and dtype.  The compositions are the tests' reference and the baseline of
+closest_points_on_mesh_torch / mesh_point_distance_torch / closest_points_to_faces_torch) for every other
+device and dtype.  The compositions are the tests' reference and the baseline of
 tools/bench_point_loss.py.
 
 Chamfer distance, for x [B, N, 3] and y [B, M, 3] (or one [M, 3] set shared by the items):
@@ -40,14 +42,28 @@ run to run (no float atomics, fixed-order sums, the same whether or not the face
 blocks); the gradient of the vertices is scattered with float atomics and agrees up to the order of float
 additions, like the sampling backward.
 
+Face-to-scan distance, the opposite direction with the same inputs:
+
+    loss_b = (1/F) sum_f min_i dist^2(p_i, T_f)
+
+Every face counts; the nearest point is the lowest index among exact float32 ties of the same float32 pair
+distance, and a degenerate face follows the same rule.  The fused forward (nr_face_point_*) chooses the point,
+forms the face's closest point to it in float64 and saves the point and the weights; the gradient holds both
+constant.  Determinism: dist2, point, weights, the loss and the gradient of the vertices (a gather over each
+vertex's corners in ascending order, no atomics) are bitwise reproducible, the same whether or not the points
+were split over several blocks; the gradient of the points is scattered with float atomics (many faces share a
+nearest point) and agrees up to the order of float additions.
+
 No call synchronises with the host in the steady state (a faces tensor is range-checked once and
-cached, as everywhere else), so a step can be captured in a HIP graph."""
+cached, as everywhere else; the first mesh_point_distance forward that needs the vertex gradient also builds
+the vertex -> corner lists of its faces tensor on the host, a device-to-host copy, and caches them), so a
+step can be captured in a HIP graph once an eager step has run."""
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .mesh_loss import _finish
-from .topology import faces_i32
+from .topology import faces_i32, vertex_adjacency
 
 CHAMFER_TILE = _lib.NR_CHAMFER_TILE  # targets the nearest-neighbour kernel stages in LDS at a time
 _DIRECTIONS = {"both": _lib.NR_CHAMFER_X_TO_Y | _lib.NR_CHAMFER_Y_TO_X, "x_to_y": _lib.NR_CHAMFER_X_TO_Y,
@@ -55,6 +71,7 @@ _DIRECTIONS = {"both": _lib.NR_CHAMFER_X_TO_Y | _lib.NR_CHAMFER_Y_TO_X, "x_to_y"
 _CHUNK_ELEMS = 1 << 24  # difference-tensor elements the compositions build at a time
 _CHUNK_PAIRS = 1 << 20  # point-face pairs the point-mesh composition tests at a time (some twenty [pairs, 3] temporaries)
 POINT_MESH_TILE, POINT_MESH_QBLOCK = _lib.NR_POINT_MESH_TILE, _lib.NR_POINT_MESH_QBLOCK  # faces per LDS tile, queries per block
+FACE_POINT_TILE, FACE_POINT_FBLOCK = _lib.NR_FACE_POINT_TILE, _lib.NR_FACE_POINT_FBLOCK  # points per LDS tile, faces per block
 
 
 def _directions(directions):
@@ -547,6 +564,166 @@ def closest_points_on_mesh(points, vertices, faces):
     with torch.no_grad():
         _, dist2, face, weights = _point_mesh_launch(_dense_y(p.detach()), v.detach().contiguous(), f, False)
     return (dist2[0], face[0], weights[0]) if single else (dist2, face, weights)
+
+
+# ---- face-to-scan distance ----
+def _nearest_point_torch(p, tri, degenerate):
+    """int64 [B, F]: the nearest point of p [B, N, 3] to every face (torch.min: the first of equal minima),
+    chunked over F."""
+    B, N, F = p.shape[0], p.shape[1], tri.shape[1]
+    step = max(1, _CHUNK_PAIRS // (N * B))
+    out = []
+    for i in range(0, F, step):
+        t, deg = tri[:, i:i + step, None], degenerate[:, i:i + step, None]
+        out.append(_point_triangle(p[:, None, :, :], t[..., 0, :], t[..., 1, :], t[..., 2, :], deg, False).min(dim=2)[1])
+    return torch.cat(out, 1)
+
+
+def _closest_to_faces_torch(p, v, fl, point):
+    """(dist2 [B, F], int64 point [B, F], weights [B, F, 3]) of the faces against p [B, N, 3]; dist2 is
+    differentiable in p and v, point (its own arg-min when None) and weights are constants."""
+    with torch.no_grad():
+        tri, degenerate = _mesh_corners(v, fl)
+        if point is None:
+            point = _nearest_point_torch(p, tri, degenerate)
+        own = p.gather(1, point[..., None].expand(-1, -1, 3))
+        weights = _point_triangle(own, tri[:, :, 0], tri[:, :, 1], tri[:, :, 2], degenerate, True)
+    c = sum(weights[..., k, None] * v[:, fl[:, k]] for k in range(3))
+    d = p.gather(1, point[..., None].expand(-1, -1, 3)) - c
+    return (d * d).sum(-1), point, weights
+
+
+def closest_points_to_faces_torch(vertices, faces, points):
+    """closest_points_to_faces as torch ops; any device and floating dtype (dist2 and weights in that dtype)."""
+    p, v, f, single = _prepare_point_mesh(points, vertices, faces)
+    with torch.no_grad():
+        dist2, point, weights = _closest_to_faces_torch(_expanded(p, v.shape[0]), v, f.long(), None)
+    point = point.to(torch.int32)
+    return (dist2[0], point[0], weights[0]) if single else (dist2, point, weights)
+
+
+def mesh_point_distance_torch(vertices, faces, points, average=False, point=None):
+    """mesh_point_distance as torch ops: the nearest point of every face from a chunked [B, f, N] point-triangle
+    test (held constant, as are the weights of the closest point), then a gather and a mean; any device and
+    floating dtype.  With point [B, F] (or [F] for single inputs) given, that assignment replaces the arg-min:
+    the closest point of the face to the given point is still computed, differentiably."""
+    p, v, f, single = _prepare_point_mesh(points, vertices, faces)
+    B = v.shape[0]
+    pb = _expanded(p, B)
+    if point is not None:
+        point = torch.as_tensor(point, device=v.device).long().reshape(B, f.shape[0])
+        if point.numel() and (int(point.min()) < 0 or int(point.max()) >= pb.shape[1]):
+            raise IndexError("point index out of range [0, %d)" % pb.shape[1])
+    dist2 = _closest_to_faces_torch(pb, v, f.long(), point)[0]
+    return _finish(dist2.mean(1), single, average)
+
+
+def _face_point_launch(p, v, f, want_loss):
+    """p as _dense_y gives it, v [B, V, 3] contiguous, f [F, 3] int32 -> (loss or None, dist2, point, weights)."""
+    B, N, V, F = v.shape[0], p.shape[-2], v.shape[1], f.shape[0]
+    dev = v.device
+    L = _lib.lib()
+    dist2 = torch.empty((B, F), dtype=torch.float32, device=dev)
+    point = torch.empty((B, F), dtype=torch.int32, device=dev)
+    weights = torch.empty((B, F, 3), dtype=torch.float32, device=dev)
+    loss = torch.empty(B, dtype=torch.float32, device=dev) if want_loss else None
+    ws = torch.empty(L.nr_face_point_workspace_bytes(B, N, F), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(L.nr_face_point_forward(_lib.ptr(p), _points_stride(p), _lib.ptr(v), _lib.ptr(f), B, N, V, F, _lib.ptr(dist2),
+                                           _lib.ptr(point), _lib.ptr(weights), _lib.ptr(loss), _lib.ptr(ws), ws.numel(),
+                                           _lib.stream_of(v)), "nr_face_point_forward")
+    return loss, dist2, point, weights
+
+
+class MeshPointFunction(torch.autograd.Function):
+    """vertices [B, V, 3] float32 contiguous on the GPU, points as _dense_y gives them, faces [F, 3] int32 ->
+    loss [B]; saves the chosen points and the weights (and the inputs, which the backward reads again).  The
+    corner lists of the vertex gather are looked up in the forward (cached per faces tensor), so the backward
+    does no host work."""
+
+    @staticmethod
+    def forward(ctx, vertices, points, faces):
+        loss, _, point, weights = _face_point_launch(points, vertices, faces, True)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ctx.save_for_backward(points, vertices, faces, point, weights)
+            ctx.corners = vertex_adjacency(faces, vertices.shape[1]) if ctx.needs_input_grad[0] else (None, None)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        need_v, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_p or need_v):
+            return None, None, None
+        p, v, f, point, weights = ctx.saved_tensors
+        B, N, V = v.shape[0], p.shape[-2], v.shape[1]
+        if need_p and p.ndim == 2:
+            raise RuntimeError("shared points that take a gradient must be passed batch-expanded")
+        g = grad_loss.to(torch.float32).contiguous()
+        gp = torch.empty((B, N, 3), dtype=torch.float32, device=v.device) if need_p else None
+        gv = torch.empty_like(v) if need_v else None
+        offsets, index = ctx.corners
+        with _lib.on_device(v.device):
+            _lib.check(_lib.lib().nr_face_point_backward(_lib.ptr(p), _points_stride(p), _lib.ptr(v), _lib.ptr(f), _lib.ptr(offsets),
+                                                         _lib.ptr(index), _lib.ptr(point), _lib.ptr(weights), _lib.ptr(g), B, N, V,
+                                                         f.shape[0], _lib.ptr(gp), _lib.ptr(gv), _lib.stream_of(v)),
+                       "nr_face_point_backward")
+        return gv, gp, None
+
+
+def mesh_point_distance(vertices, faces, points, average=False):
+    """(1/F) sum_f min_i dist^2(p_i, T_f) per item, T_f the triangle f as a closed set: the mean over the faces of
+    the squared distance from the face to its nearest point, the term that keeps a mesh from growing surface
+    where a scan has no points (the face -> point half of a point-mesh face distance).  [B] for vertices
+    [B, V, 3], a 0-dim tensor for [V, 3] or with average=True (the mean over the items).  points is [B, N, 3],
+    or [N, 3]: alone with a single mesh, shared by the items of a batched one (read in place; expanded only
+    when it takes a gradient, so that torch's expand backward sums the items).  faces is [F, 3], shared
+    (out-of-range indices raise IndexError).  N = 0, F = 0 and differing batch sizes raise ValueError; the
+    inputs are taken to be finite.
+
+    Every face counts.  The lowest point index wins among exact float32 ties; the pair distance and the
+    degenerate-face rule are point_mesh_distance's.  The gradient holds the point choice and the barycentric
+    weights w of the closest point c_f constant: vertex j takes -g_b (2/F) sum w_fk (p - c_f) over the corners
+    (f, k) that are j, point i takes g_b (2/F) sum (p_i - c_f) over the faces that chose it.  float32 GPU
+    tensors run the fused kernels (nr_face_point_*): the loss and the vertex gradient are bitwise
+    reproducible, the point gradient is scattered with float atomics (module docstring).  Everything else
+    runs mesh_point_distance_torch."""
+    if not _fused(vertices, points):
+        return mesh_point_distance_torch(vertices, faces, points, average)
+    p, v, f, single = _prepare_point_mesh(points, vertices, faces)
+    if p.ndim == 2 and p.requires_grad and torch.is_grad_enabled():
+        p = p[None].expand(v.shape[0], -1, -1)
+    return _finish(MeshPointFunction.apply(v.contiguous(), _dense_y(p), f), single, average)
+
+
+def closest_points_to_faces(vertices, faces, points):
+    """For every face of the mesh its nearest point of points ([B, N, 3], or [N, 3] alone or shared): (dist2
+    [B, F] float32, point [B, F] int32: the nearest point, the lowest index among exact ties, weights [B, F, 3]
+    float32: the barycentric weights of the face's closest point to it over the face's corners).  dist2 is the
+    squared distance between exactly those two.  All three are detached."""
+    if not _fused(vertices, points):
+        return closest_points_to_faces_torch(vertices, faces, points)
+    p, v, f, single = _prepare_point_mesh(points, vertices, faces)
+    with torch.no_grad():
+        _, dist2, point, weights = _face_point_launch(_dense_y(p.detach()), v.detach().contiguous(), f, False)
+    return (dist2[0], point[0], weights[0]) if single else (dist2, point, weights)
+
+
+class MeshPointLoss(torch.nn.Module):
+    """mesh_point_distance from the mesh given to forward to an optional fixed point set held by the module (a
+    buffer: it moves with .to()); forward(vertices, faces) uses it, forward(vertices, faces, points) the given
+    points."""
+
+    def __init__(self, points=None, average=False):
+        super().__init__()
+        self.register_buffer("points", None if points is None else torch.as_tensor(points).detach().clone())
+        self.average = average
+
+    def forward(self, vertices, faces, points=None):
+        points = self.points if points is None else points
+        if points is None:
+            raise ValueError("MeshPointLoss needs points: pass them, or construct the module with a point set")
+        return mesh_point_distance(vertices, faces, points, self.average)
 
 
 class PointMeshLoss(torch.nn.Module):

@@ -6,6 +6,10 @@ The point-mesh cells time point_mesh_distance (gradient to the vertices) from N 
 samples of a differently jittered copy, moved by N(0, 0.01)) to the icosphere L4 at N = 25000, B = 1 and
 16, and to the torus at N = 100000, B = 1.  Their composition tests B N F point-face pairs in chunks of
 2^20, several seconds a step on the torus: it runs 3 timed steps after 1 warm-up, eager only.
+The mesh-point cells time mesh_point_distance (the opposite direction, gradient to the vertices) on the same
+three shapes and scan points and on examples/example_scan_fit.py's own (icosphere L3, F 1280, N 5000, B 1), with
+the same protocol; the summary gives their point-face tests per second beside the point-mesh cell of the same
+shape (the arithmetic per test is identical) and the ratio of the two.
 
 Every (cell, path) runs in a child process of its own under `timeout`; the first one that fails ends the
 run.  Per cell: eager wall-clock per step (host time of a synchronised loop), eager GPU time per step
@@ -16,9 +20,11 @@ the acceptance cells (fused not slower than the composition), the pair rate of t
 kernel's algorithmic bytes and the registers the compiler reports for it; for the point-mesh cells also the
 point-face tests per second (B N F over the fused graph-replay time, backward included).
 
-    python tools/bench_point_loss.py [--steps 100] [--warmup 20] [--out FILE] [--only chamfer|sample|point_mesh]
+    python tools/bench_point_loss.py [--steps 100] [--warmup 20] [--out FILE] [--only chamfer|sample|point_mesh|mesh_point]
 
 With --only the rows and a summary of those cells alone are appended to --out; without it the file is rewritten.
+--only mesh_point runs the point_mesh cells again as well, so that both rates come from one run: the file then
+holds a second set of point_mesh rows, and the ones to read beside the mesh_point rows are those just before them.
 """
 import argparse
 import json
@@ -32,23 +38,30 @@ sys.path.insert(0, ROOT)
 
 SHAPES = {"ico4_b64": ("ico4", 64), "torus_b1": ("torus", 1)}
 PM_SHAPES = {"ico4_n25k_b1": ("ico4", 1, 25000), "ico4_n25k_b16": ("ico4", 16, 25000), "torus_n100k_b1": ("torus", 1, 100000)}
-CELLS = [("chamfer", s) for s in SHAPES] + [("sample", s) for s in SHAPES] + [("point_mesh", s) for s in PM_SHAPES]
+# the point-mesh shapes and examples/example_scan_fit.py's own (icosphere L3: V 642, F 1280; 5000 scan points)
+MP_SHAPES = dict(PM_SHAPES, ico3_n5k_b1=("ico3", 1, 5000))
+PAIR_SHAPES = {"point_mesh": PM_SHAPES, "mesh_point": MP_SHAPES}  # the cells that test B N F point-face pairs
+CELLS = ([("chamfer", s) for s in SHAPES] + [("sample", s) for s in SHAPES] + [("point_mesh", s) for s in PM_SHAPES] +
+         [("mesh_point", s) for s in MP_SHAPES])
 PM_COMPOSITION_STEPS, PM_COMPOSITION_WARMUP = 3, 1
 # VALU instructions of k_point_face_nn's inner loop per point-face test: 230 per face and four queries in the gfx950
 # assembly (hipcc -S with the build's flags; tools/isa_cost.py weighs the same block)
 PM_LOOP_VALU_PER_TEST = 57.5
+# the same for k_face_point_nn: 229 per four points of its unrolled loop (bc = ac - ab is loop-invariant there)
+FP_LOOP_VALU_PER_TEST = 57.25
 PATHS = ("fused", "composition")
 SAMPLES = 10000
 # VGPRs per lane of each kernel as hipcc reports them for gfx950 (-Rpass-analysis=kernel-resource-usage on
 # csrc/nr_raster.hip with the build's flags); 78 allocates 80: 6 waves per SIMD, the rest run at 8
 KERNEL_VGPRS = {"k_chamfer_nn": 78, "k_chamfer_combine": 10, "k_chamfer_sum": 18, "k_chamfer_bwd": 32,
                 "k_sample_scan": 56, "k_sample_points": 26, "k_sample_points_bwd": 19,
-                "k_point_face_records": 52, "k_point_face_nn": 66, "k_point_face_finish": 100, "k_point_mesh_bwd": 30}
+                "k_point_face_records": 52, "k_point_face_nn": 66, "k_point_face_finish": 100, "k_point_mesh_bwd": 30,
+                "k_face_point_nn": 50, "k_face_point_finish": 100, "k_face_point_bwd_vertices": 36, "k_face_point_bwd_points": 24}
 
 
 def mesh(kind):
     from neural_renderer_v2_pytorch_amd import synthetic
-    return synthetic.torus() if kind == "torus" else synthetic.icosphere(4)
+    return synthetic.torus() if kind == "torus" else synthetic.icosphere(3 if kind == "ico3" else 4)
 
 
 def kernel_bytes(B, N, M, F, S):
@@ -74,14 +87,25 @@ def point_mesh_bytes(B, N, F):
     }
 
 
+def face_point_bytes(B, N, F, V):
+    """The same for the mesh-point kernels (the vertex gather reads a face's arrays once per corner)."""
+    return {
+        "k_point_face_records": 4 * (B * F * 9 + F * 3 + B * F * 24),
+        "k_face_point_nn": 4 * (B * N * 3 + B * F * 24 + 2 * B * F),
+        "k_face_point_finish": 4 * (B * F * (1 + 3 + 3 + 9) + B * F * (1 + 1 + 3)),
+        "k_face_point_bwd_vertices": 4 * (V + 1 + 3 * F + 3 * B * F * (1 + 3 + 3 + 3 + 9) + B + B * V * 3),
+    }
+
+
 def cell(what, shape, path, warmup, steps):
     import numpy as np
     import torch
     import neural_renderer_v2_pytorch_amd as nr
     from neural_renderer_v2_pytorch_amd import synthetic
 
-    kind, B = (PM_SHAPES if what == "point_mesh" else SHAPES)[shape][:2]
-    composed_pm = what == "point_mesh" and path == "composition"
+    pairs = what in PAIR_SHAPES
+    kind, B = (PAIR_SHAPES[what] if pairs else SHAPES)[shape][:2]
+    composed_pm = pairs and path == "composition"
     if composed_pm:
         warmup, steps = min(warmup, PM_COMPOSITION_WARMUP), min(steps, PM_COMPOSITION_STEPS)
     dev = torch.device("cuda:0")
@@ -93,14 +117,17 @@ def cell(what, shape, path, warmup, steps):
         y = torch.as_tensor(synthetic.jittered(v, B, sigma=0.005, seed_base=2000), device=dev)
         g = torch.as_tensor(np.random.RandomState(0).normal(size=B).astype(np.float32), device=dev)
         fn = nr.chamfer_distance if path == "fused" else nr.chamfer_distance_torch
-    elif what == "point_mesh":
-        N = PM_SHAPES[shape][2]
+    elif pairs:
+        N = PAIR_SHAPES[what][shape][2]
         u = torch.as_tensor(np.random.RandomState(1).uniform(0, 1, (B, N, 3)).astype(np.float32), device=dev)
         other = torch.as_tensor(synthetic.jittered(v, B, sigma=0.005, seed_base=2000), device=dev)
         noise = torch.as_tensor(np.random.RandomState(2).normal(scale=0.01, size=(B, N, 3)).astype(np.float32), device=dev)
         y = (nr.sample_points(other, faces, N, u=u) + noise).contiguous()
         g = torch.as_tensor(np.random.RandomState(0).normal(size=B).astype(np.float32), device=dev)
-        fn = nr.point_mesh_distance if path == "fused" else nr.point_mesh_distance_torch
+        if what == "point_mesh":
+            fn = nr.point_mesh_distance if path == "fused" else nr.point_mesh_distance_torch
+        else:
+            fn = nr.mesh_point_distance if path == "fused" else nr.mesh_point_distance_torch
     else:
         u = torch.as_tensor(np.random.RandomState(1).uniform(0, 1, (B, SAMPLES, 3)).astype(np.float32), device=dev)
         g = torch.as_tensor(np.random.RandomState(0).normal(size=(B, SAMPLES, 3)).astype(np.float32), device=dev)
@@ -112,7 +139,8 @@ def cell(what, shape, path, warmup, steps):
     def step():
         # returns a detached result: no reference to the autograd graph outlives a step (bench_mesh_loss.py)
         x.grad = None
-        out = fn(x, y) if what == "chamfer" else fn(y, x, faces) if what == "point_mesh" else fn(x, faces, SAMPLES, u=u)
+        out = (fn(x, y) if what == "chamfer" else fn(y, x, faces) if what == "point_mesh" else fn(x, faces, y) if what == "mesh_point"
+               else fn(x, faces, SAMPLES, u=u))
         out.backward(g)
         return out.detach()
 
@@ -164,14 +192,14 @@ def cell(what, shape, path, warmup, steps):
     peak = torch.cuda.max_memory_allocated() - base
     note("eager done")
     # the sampling backward adds with float atomics: its gradient is compared to a tolerance, not bitwise
-    # (so does the point-mesh backward to the vertices)
+    # (so does the point-mesh backward to the vertices; the mesh-point backward gathers them: bitwise)
     if composed_pm:
         same = None
-    elif what == "chamfer":
+    elif what in ("chamfer", "mesh_point"):
         same = bool(torch.equal(graph_out, eager_out) and torch.equal(graph_grad, x.grad))
     else:
         same = bool(torch.equal(graph_out, eager_out) and torch.allclose(graph_grad, x.grad, rtol=1e-4, atol=1e-6))
-    return {"cell": what, "shape": shape, "path": path, "B": B, "N": PM_SHAPES[shape][2] if what == "point_mesh" else V, "M": V, "F": F,
+    return {"cell": what, "shape": shape, "path": path, "B": B, "N": PAIR_SHAPES[what][shape][2] if pairs else V, "M": V, "F": F,
             "S": SAMPLES if what == "sample" else 0, "steps": steps,
             "eager_wall_ms": round(wall, 4), "eager_gpu_ms": round(gpu, 4),
             "graph_ms": round(float(np.median(reps)), 4) if reps else None,
@@ -185,7 +213,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "point_loss_bench.jsonl"))
     ap.add_argument("--timeout", type=int, default=240, help="seconds per cell")
-    ap.add_argument("--only", choices=("chamfer", "sample", "point_mesh"), help="these cells alone, appended to --out")
+    ap.add_argument("--only", choices=("chamfer", "sample", "point_mesh", "mesh_point"),
+                    help="these cells alone, appended to --out (mesh_point also runs the point_mesh cells, its yardstick)")
     ap.add_argument("--cell", nargs=3, metavar=("WHAT", "SHAPE", "PATH"), help="run one cell in this process")
     a = ap.parse_args()
     if a.cell:
@@ -193,7 +222,9 @@ def main():
         return 0
     rows = {}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    cells = [c for c in CELLS if a.only in (None, c[0])]
+    # the mesh_point cells are read beside the point_mesh cell of the same shape from the same run
+    wanted = (None, a.only, "point_mesh") if a.only == "mesh_point" else (None, a.only)
+    cells = [c for c in CELLS if a.only is None or c[0] in wanted]
     with open(a.out, "a" if a.only else "w") as out:
         for what, shape in cells:
             for path in PATHS:
@@ -208,8 +239,10 @@ def main():
                 out.write(line + "\n")
                 out.flush()
                 print(line, flush=True)
-        summary = {"summary": {}, "pairs_per_s": {}, "point_face_tests_per_s": {}, "peak_step_bytes": {}, "kernel_bytes": {},
-                   "kernel_vgprs": KERNEL_VGPRS, "point_face_loop_valu_per_test": PM_LOOP_VALU_PER_TEST}
+        summary = {"summary": {}, "pairs_per_s": {}, "point_face_tests_per_s": {}, "mesh_point_rate_over_point_mesh": {},
+                   "peak_step_bytes": {}, "kernel_bytes": {},
+                   "kernel_vgprs": KERNEL_VGPRS, "point_face_loop_valu_per_test": PM_LOOP_VALU_PER_TEST,
+                   "face_point_loop_valu_per_test": FP_LOOP_VALU_PER_TEST}
         for what, shape in cells:
             fused, comp = rows[(what, shape, "fused")], rows[(what, shape, "composition")]
             name = "%s/%s" % (what, shape)
@@ -226,6 +259,13 @@ def main():
             if what == "point_mesh":
                 summary["point_face_tests_per_s"][name] = round(1.0 * fused["B"] * fused["N"] * fused["F"] / (fused["graph_ms"] * 1e-3), 1)
                 summary["kernel_bytes"][shape] = point_mesh_bytes(fused["B"], fused["N"], fused["F"])
+            if what == "mesh_point":
+                rate = round(1.0 * fused["B"] * fused["N"] * fused["F"] / (fused["graph_ms"] * 1e-3), 1)
+                summary["point_face_tests_per_s"][name] = rate
+                sibling = summary["point_face_tests_per_s"].get("point_mesh/%s" % shape)
+                if sibling:
+                    summary["mesh_point_rate_over_point_mesh"][shape] = round(rate / sibling, 3)
+                summary["kernel_bytes"]["mesh_point/" + shape] = face_point_bytes(fused["B"], fused["N"], fused["F"], fused["M"])
         line = json.dumps(summary)
         out.write(line + "\n")
         print(line)
