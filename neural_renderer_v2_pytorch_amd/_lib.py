@@ -187,8 +187,9 @@ def lib():
         raise RuntimeError("neural_renderer_v2_pytorch_amd: HIP library %s is missing; build it with "
                            "__graft_entry__.build() (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_adam_*, nr_attributes_*, point-loss, nr_point_mesh_* and nr_face_point_* entry points): a library built before them
-    # still reports the version this binding expects
+    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_adam_*, nr_attributes_*,
+    # point-loss entry points and the two point / mesh distance directions, nr_point_mesh_* and nr_face_point_*):
+    # a library built before them still reports the version this binding expects
     missing = [name for name in EXPORTS if not hasattr(L, name)]
     if missing:
         raise RuntimeError("neural_renderer_v2_pytorch_amd: %s lacks %s; this binding needs a newer build of the "
@@ -211,8 +212,9 @@ def lib():
 
 
 def last_launch(kernel):
-    """(threads per block, NR_LAUNCH_* flags) of the latest launch of `kernel` ("k_raster_fwd",
-    "k_raster_bwd", "k_chamfer_nn", "k_point_face_nn" or "k_face_point_nn") in this process: the variant the library actually ran."""
+    """(threads per block, NR_LAUNCH_* flags) of the latest launch of `kernel` in this process: the variant the
+    library actually ran.  kernel: "k_raster_fwd", "k_raster_bwd", "k_chamfer_nn", or the nearest-neighbour loop of a
+    point / mesh distance direction, "k_point_face_nn" or "k_face_point_nn"."""
     t, f = c_int(), c_int()
     check(lib().nr_last_launch(kernel.encode(), ctypes.byref(t), ctypes.byref(f)), "nr_last_launch")
     return t.value, f.value

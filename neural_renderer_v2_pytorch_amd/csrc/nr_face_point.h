@@ -3,21 +3,11 @@
 // Part of nr_raster.hip (one translation unit); see that file, include/nr_raster.h (the formulas) and
 // DESIGN.md section 4 ("Point losses").
 //
-// Conventions (those of nr_point_mesh.h): 256-thread blocks that never straddle an item, plain pointers,
-// every output fully written, no host synchronisation.  The forward uses no float atomics and every sum
-// has one fixed order: dist2, point, weights and the loss are bitwise reproducible from run to run, and so
-// is the vertex gradient, a gather over each vertex's corners in ascending order.  The point gradient is
-// scattered with float atomics (as k_sample_points_bwd does; many faces share a nearest point): it agrees
-// from run to run up to the order of float additions.
-//
-// The pair test and the float64 closest point are nr_point_mesh.h's own functions (pm_pair_dist2,
-// pm_closest64), and the face records are those k_point_face_records writes: the two directions choose by
-// the same bits and apply the same degenerate-face rules.
-//
-// Limits (checked by the host entry points): N, F, V >= 1; B <= 65535 (grid.y); B * F <= INT_MAX - 4096,
-// B * N and 3 B V <= INT_MAX.  The saved point indices are written by k_face_point_nn / k_chamfer_combine
-// and are always inside [0, N), whatever the coordinates hold (NaN compares false and keeps the first point
-// of the range), so the finish and the backward never read out of range.
+// Only what is this direction's own: the nearest-neighbour loop with its blocking and the two backward kernels.
+// The face records, the pair test, the loop's arguments, the finish, the gradient term, the conventions and
+// the limits are nr_point_mesh.h's.  Here the vertex gradient is the reproducible one, a gather over each
+// vertex's corners in ascending order, and the point gradient is scattered with float atomics (many faces
+// share a nearest point).
 #pragma once
 
 #pragma clang fp contract(off)
@@ -34,24 +24,13 @@ static_assert(FP_TILE <= PL_BLOCK, "a tile is staged by one pass of the block, o
 
 LaunchSlot g_last_face_point;
 
-// One launch: for every face its nearest point.
-struct FpArgs {
-    const float* points;     // [B, N, 3], item stride p_stride (elements; 0 = shared)
-    long long p_stride;
-    const float* records;    // [B, F, PM_REC], as k_point_face_records writes them
-    int N, F;
-    int nsplit;              // point ranges per face block (1: results go straight to the final arrays)
-    float* dist2;            // [B, F]  (nsplit == 1)  or the partials [B, nsplit, F]
-    int32_t* point;          // the same shape
-};
-
 // grid: (face blocks * nsplit, B).  Block (fb, split) keeps the records of the FP_FBLOCK faces fb * FP_FBLOCK +
 // k * 256 + thread (k < FP_Q) in registers (bc = ac - ab formed once, in float32, as k_point_face_nn's loop
 // forms it) and streams the points [lo, hi) of its split through LDS in tiles of FP_TILE.  Every lane reads
 // the same point (one 16-byte broadcast read, no bank conflicts) and tests it with pm_pair_dist2.  (best d2,
 // best i) starts at (+inf, lo) and advances on a strict < over ascending i: the lowest index wins among exact
 // ties, and the index stays inside the range whatever the coordinates hold.
-__global__ __launch_bounds__(PL_BLOCK) void k_face_point_nn(FpArgs d) {
+__global__ __launch_bounds__(PL_BLOCK) void k_face_point_nn(PairArgs d) {
     __shared__ float4 spt[FP_TILE];
     const int lin = blockIdx.x;
     const int fb = lin / d.nsplit, split = lin - fb * d.nsplit;
@@ -102,44 +81,9 @@ __global__ __launch_bounds__(PL_BLOCK) void k_face_point_nn(FpArgs d) {
         const int f = fb * FP_FBLOCK + k * PL_BLOCK + (int)threadIdx.x;
         if (f < d.F) {
             d.dist2[base + f] = best[k];
-            d.point[base + f] = bi[k];
+            d.index[base + f] = bi[k];
         }
     }
-}
-
-// One thread per (item, face): the closest point of the face to its winning point, in float64 from the float32
-// values (pm_closest64; the loop's float32 distance only chose the point).  weights and dist2 are rounded once.
-// Each of dist2, point, weights may be null.  grid: (ceil(F / 256), B).
-__global__ __launch_bounds__(PL_BLOCK) void k_face_point_finish(const float* __restrict__ points, long long p_stride,
-                                                                const float* __restrict__ vertices, const int32_t* __restrict__ faces,
-                                                                const int32_t* __restrict__ nearest, int V, int F,
-                                                                float* __restrict__ dist2, int32_t* __restrict__ point,
-                                                                float* __restrict__ weights) {
-    const int f = blockIdx.x * PL_BLOCK + threadIdx.x, b = blockIdx.y;
-    if (f >= F) return;
-    const long long n = (long long)b * F + f;
-    const int i = nearest[n];
-    const float* p = points + (long long)b * p_stride + (long long)i * 3;
-    const float* vb = vertices + (long long)b * V * 3;
-    const int i0 = faces[3 * (long long)f], i1 = faces[3 * (long long)f + 1], i2 = faces[3 * (long long)f + 2];
-    double w[3];
-    const double d2 = pm_closest64(p, i0, i1, i2, vb + (long long)i0 * 3, vb + (long long)i1 * 3, vb + (long long)i2 * 3, w);
-    if (dist2) dist2[n] = (float)d2;
-    if (point) point[n] = i;
-    if (weights) weights[n * 3] = (float)w[0], weights[n * 3 + 1] = (float)w[1], weights[n * 3 + 2] = (float)w[2];
-}
-
-// s (p - c) of face f of item b: c = (w0 a + w1 b) + w2 c of the saved weights, p the saved nearest point.
-__device__ __forceinline__ void fp_face_term(const float* __restrict__ pp, const float* __restrict__ vb, const int32_t* __restrict__ faces,
-                                             const int32_t* __restrict__ point, const float* __restrict__ weights, long long n, int f,
-                                             float s, float* g, float* w) {
-    const float* p = pp + (long long)point[n] * 3;
-    const float* pa = vb + (long long)faces[3 * (long long)f] * 3;
-    const float* pb = vb + (long long)faces[3 * (long long)f + 1] * 3;
-    const float* pc = vb + (long long)faces[3 * (long long)f + 2] * 3;
-    w[0] = weights[n * 3], w[1] = weights[n * 3 + 1], w[2] = weights[n * 3 + 2];
-#pragma unroll
-    for (int k = 0; k < 3; k++) g[k] = s * (p[k] - ((w[0] * pa[k] + w[1] * pb[k]) + w[2] * pc[k]));
 }
 
 // One thread per (item, vertex): walks the vertex's corners 3 f + k in ascending order (the CSR list of
@@ -162,7 +106,8 @@ __global__ __launch_bounds__(PL_BLOCK) void k_face_point_bwd_vertices(const floa
         const int corner = corner_index[e];
         const int f = corner / 3, k = corner - 3 * f;
         float g[3], w[3];
-        fp_face_term(pp, vb, faces, point, weights, (long long)b * F + f, f, s, g, w);
+        const long long n = (long long)b * F + f;
+        pm_face_term(pp + (long long)point[n] * 3, vb, faces, weights, n, f, s, g, w);
         const float wk = k == 0 ? w[0] : k == 1 ? w[1] : w[2];
 #pragma unroll
         for (int c = 0; c < 3; c++) acc[c] += -(wk * g[c]);
@@ -182,7 +127,7 @@ __global__ __launch_bounds__(PL_BLOCK) void k_face_point_bwd_points(const float*
     if (f >= F) return;
     const long long n = (long long)b * F + f;
     float g[3], w[3];
-    fp_face_term(points + (long long)b * p_stride, vertices + (long long)b * V * 3, faces, point, weights, n, f,
+    pm_face_term(points + (long long)b * p_stride + (long long)point[n] * 3, vertices + (long long)b * V * 3, faces, weights, n, f,
                  grad_loss[b] * (2.f / (float)F), g, w);
     float* o = grad_points + ((long long)b * N + point[n]) * 3;
 #pragma unroll

@@ -120,7 +120,7 @@ HaloLayout halo_layout(int B, int S, int C) {
     return {flags, flags + (((size_t)B * make_geom(0, S).nbins + 3) & ~size_t(3))};
 }
 
-// How a nearest-neighbour launch (a chamfer direction: PL_*, point-to-surface: PM_*) is cut: query blocks per
+// How a nearest-neighbour launch (a chamfer direction: PL_*, a PairDir: PM_* or FP_*) is cut: query blocks per
 // item, and target ranges per query block (more than one -- the split path -- while the launch has fewer
 // than split_blocks blocks and every range still holds at least a full tile of targets: few queries against
 // many targets would otherwise leave most of the chip idle).  Results do not depend on the cut.
@@ -150,31 +150,36 @@ ChamferLayout chamfer_layout(int B, int nq, int nt) {
     return {p, c.take((size_t)B * nq * 4), c.take_if(p.nsplit > 1, part), c.take_if(p.nsplit > 1, part), c.off};
 }
 
-// point-to-surface: records [B, F, PM_REC], the nearest face [B, N], the loop's and the finish's dist2 [B, N]
-// each, and on the split path the partial d2 and f [B, nsplit, N] each
-struct PointMeshLayout {
-    SplitPlan plan;
-    size_t records, nearest, loop_d2, fin_d2, part_d2, part_f, total;
+// The two directions of the point / mesh distance, which share one host path (nr_raster.hip): point -> face (for
+// every point its nearest face, nr_point_mesh.h) and face -> point (for every face its nearest point,
+// nr_face_point.h).  Everything that tells them apart on the host is stated here.
+struct PairDir {
+    bool face_query;                   // the queries are the F faces and the targets the N points; else the reverse
+    int qblock, tile, split_blocks;    // the nearest-neighbour launch's split plan
+    int split_flag;                    // NR_LAUNCH_* of a split launch
+    LaunchSlot* slot;                  // what nr_last_launch reads
+    decltype(&k_point_face_nn) nn;     // the nearest-neighbour loop
+    decltype(&k_pair_finish<false>) finish;
+    const char *nn_name, *finish_name, *name;  // the two kernels as check_launch reports them; the direction in messages
+    int queries(int N, int F) const { return face_query ? F : N; }
+    int targets(int N, int F) const { return face_query ? N : F; }
 };
-PointMeshLayout point_mesh_layout(int B, int N, int F) {
-    const SplitPlan p = split_plan(B, N, F, PM_QBLOCK, PM_TILE, PM_SPLIT_BLOCKS);
-    const size_t bn = (size_t)B * N * 4, part = bn * p.nsplit;
-    Cutter c;
-    return {p, c.take((size_t)B * F * PM_REC * 4), c.take(bn), c.take(bn), c.take(bn), c.take_if(p.nsplit > 1, part),
-            c.take_if(p.nsplit > 1, part), c.off};
-}
+const PairDir POINT_FACE = {false, PM_QBLOCK, PM_TILE, PM_SPLIT_BLOCKS, NR_LAUNCH_SPLIT_FACES, &g_last_point_mesh,
+                            k_point_face_nn, k_pair_finish<false>, "k_point_face_nn", "k_point_face_finish", "point_mesh"};
+const PairDir FACE_POINT = {true, FP_FBLOCK, FP_TILE, FP_SPLIT_BLOCKS, NR_LAUNCH_SPLIT_POINTS, &g_last_face_point,
+                            k_face_point_nn, k_pair_finish<true>, "k_face_point_nn", "k_face_point_finish", "face_point"};
 
-// face-to-scan: records [B, F, PM_REC], the nearest point [B, F], the loop's and the finish's dist2 [B, F] each,
-// and on the split path the partial d2 and i [B, nsplit, F] each (the faces are the queries, the points the targets)
-struct FacePointLayout {
+// either direction, nq its queries per item: records [B, F, PM_REC], the nearest target [B, nq], the loop's and
+// the finish's dist2 [B, nq] each, and on the split path the partial d2 and index [B, nsplit, nq] each
+struct PairLayout {
     SplitPlan plan;
-    size_t records, nearest, loop_d2, fin_d2, part_d2, part_i, total;
+    size_t records, nearest, loop_d2, fin_d2, part_d2, part_index, total;
 };
-FacePointLayout face_point_layout(int B, int N, int F) {
-    const SplitPlan p = split_plan(B, F, N, FP_FBLOCK, FP_TILE, FP_SPLIT_BLOCKS);
-    const size_t bf = (size_t)B * F * 4, part = bf * p.nsplit;
+PairLayout pair_layout(const PairDir& dir, int B, int N, int F) {
+    const SplitPlan p = split_plan(B, dir.queries(N, F), dir.targets(N, F), dir.qblock, dir.tile, dir.split_blocks);
+    const size_t bq = (size_t)B * dir.queries(N, F) * 4, part = bq * p.nsplit;
     Cutter c;
-    return {p, c.take((size_t)B * F * PM_REC * 4), c.take(bf), c.take(bf), c.take(bf), c.take_if(p.nsplit > 1, part),
+    return {p, c.take((size_t)B * F * PM_REC * 4), c.take(bq), c.take(bq), c.take(bq), c.take_if(p.nsplit > 1, part),
             c.take_if(p.nsplit > 1, part), c.off};
 }
 

@@ -1,18 +1,23 @@
 // nr_point_mesh.h -- point-to-surface distance: for every point its closest point on the closest
-// triangle of a mesh, forward and backward
+// triangle of a mesh, forward and backward; and what the opposite direction (nr_face_point.h: for every
+// triangle its nearest point) shares with it: the face records, the pair test, the argument struct of the
+// two nearest-neighbour loops, the float64 closest point, the finish kernel and the gradient term.  The
+// two directions so choose by the same bits and apply the same degenerate-face rules.
 // Part of nr_raster.hip (one translation unit); see that file, include/nr_raster.h (the formulas) and
 // DESIGN.md section 4 ("Point losses").
 //
 // Conventions (those of nr_point_loss.h): 256-thread blocks that never straddle an item, plain pointers,
 // every output fully written, no host synchronisation.  The forward uses no float atomics and every sum
-// has one fixed order: dist2, face, weights, the loss and the point gradient are bitwise reproducible
-// from run to run.  The vertex gradient is scattered with float atomics (as k_sample_points_bwd does):
-// it agrees from run to run up to the order of float additions.
+// has one fixed order: dist2, the index, weights, the loss and the gradient of the queries' side (the points
+// here, the vertices in nr_face_point.h) are bitwise reproducible from run to run.  The other side's gradient
+// is scattered with float atomics (as k_sample_points_bwd does): it agrees from run to run up to the order of
+// float additions.
 //
-// Limits (checked by the host entry points): N, F, V >= 1; B <= 65535 (grid.y); B * N <= INT_MAX - 4096,
-// B * F and 3 B V <= INT_MAX.  The saved face indices are written by k_point_face_nn /
-// k_chamfer_combine and are always inside [0, F), whatever the coordinates hold (NaN compares false
-// and keeps the first face of the range), so the finish and the backward never read out of range.
+// Limits (checked by the host entry points), the queries being the points here and the faces in
+// nr_face_point.h: N, F, V >= 1; B <= 65535 (grid.y); B * queries <= INT_MAX - 4096, B * targets and 3 B V <=
+// INT_MAX.  The saved indices are written by the nearest-neighbour loop / k_chamfer_combine and are always
+// inside the targets' range, whatever the coordinates hold (NaN compares false and keeps the first target of
+// the range), so the finish and the backward never read out of range.
 #pragma once
 
 #pragma clang fp contract(off)
@@ -109,10 +114,9 @@ __device__ __forceinline__ float pm_segment(float rx, float ry, float rz, float 
     return fmaf(dz, dz, fmaf(dy, dy, dx * dx));
 }
 
-// The float32 point-face test of both nearest-neighbour loops (k_point_face_nn here, k_face_point_nn in
-// nr_face_point.h): the squared distance from the point q to the face of one record (A .. NN its six
-// 16-byte pieces, bc = ac - ab in float32).  Branch-free: the least of the distances to the three edges and,
-// where the projection falls inside, to the plane.  One body, so the two directions choose by the same bits.
+// The float32 point-face test of both nearest-neighbour loops: the squared distance from the point q to the
+// face of one record (A .. NN its six 16-byte pieces, bc = ac - ab in float32).  Branch-free: the least of the
+// distances to the three edges and, where the projection falls inside, to the plane.
 __device__ __forceinline__ float pm_pair_dist2(float qx, float qy, float qz, const float4& A, const float4& AB, const float4& AC,
                                                const float4& GV, const float4& GW, const float4& NN, float bcx, float bcy,
                                                float bcz) {
@@ -128,15 +132,16 @@ __device__ __forceinline__ float pm_pair_dist2(float qx, float qy, float qz, con
     return fminf(fminf(e0, e1), fminf(e2, plane));
 }
 
-// One direction of work: for every query point its nearest face.
-struct PmArgs {
+// One nearest-neighbour launch of either direction: for every query (a point in k_point_face_nn, a face in
+// k_face_point_nn) its nearest target (a face, a point), nq queries per item.
+struct PairArgs {
     const float* points;     // [B, N, 3], item stride p_stride (elements; 0 = shared)
     long long p_stride;
-    const float* records;    // [B, F, PM_REC]
+    const float* records;    // [B, F, PM_REC], as k_point_face_records writes them
     int N, F;
-    int nsplit;              // face ranges per query block (1: results go straight to the final arrays)
-    float* dist2;            // [B, N]  (nsplit == 1)  or the partials [B, nsplit, N]
-    int32_t* face;           // the same shape
+    int nsplit;              // target ranges per query block (1: results go straight to the final arrays)
+    float* dist2;            // [B, nq]  (nsplit == 1)  or the partials [B, nsplit, nq]
+    int32_t* index;          // the same shape
 };
 
 // grid: (query blocks * nsplit, B).  Block (qb, split) keeps the PM_QBLOCK queries qb * PM_QBLOCK + k * 256 +
@@ -147,7 +152,7 @@ struct PmArgs {
 // plane.  Every candidate is the distance to a point of the face itself, so an error in an edge parameter
 // or in (v, w) enters the result only squared.  (best d2, best f) advances on a strict < over ascending f:
 // the lowest index wins among exact ties.
-__global__ __launch_bounds__(PL_BLOCK) void k_point_face_nn(PmArgs d) {
+__global__ __launch_bounds__(PL_BLOCK) void k_point_face_nn(PairArgs d) {
     __shared__ __attribute__((aligned(16))) float srec[PM_TILE * PM_REC];
     const int lin = blockIdx.x;
     const int qb = lin / d.nsplit, split = lin - qb * d.nsplit;
@@ -195,7 +200,7 @@ __global__ __launch_bounds__(PL_BLOCK) void k_point_face_nn(PmArgs d) {
         const int i = qb * PM_QBLOCK + k * PL_BLOCK + (int)threadIdx.x;
         if (i < d.N) {
             d.dist2[base + i] = best[k];
-            d.face[base + i] = bf[k];
+            d.index[base + i] = bf[k];
         }
     }
 }
@@ -210,9 +215,8 @@ __device__ __forceinline__ double pm_segment64(const double* r, const double* e,
     return dx * dx + dy * dy + dz * dz;
 }
 
-// The float64 closest point of both finishes (k_point_face_finish here, k_face_point_finish in
-// nr_face_point.h): the closest point of the face (corners pa, pb, pc with the indices i0, i1, i2) to p, formed
-// in float64 from the float32 values.  w takes its barycentric weights (unrounded); returns |p - (w0 a + w1 b +
+// The float64 closest point of the finish: the closest point of the face (corners pa, pb, pc with the indices
+// i0, i1, i2) to p, formed in float64 from the float32 values.  w takes its barycentric weights (unrounded); returns |p - (w0 a + w1 b +
 // w2 c)|^2.  A regular face: the plane's closest point where it falls inside, else the nearest of the three
 // edges (ab, ac, bc in this order, the first among equals).  A degenerate face (pm_degenerate): its longest edge
 // in the same order, the third corner's weight 0; a point (all corners equal) gives (1, 0, 0).
@@ -249,31 +253,46 @@ __device__ __forceinline__ double pm_closest64(const float* p, int i0, int i1, i
     return (dd[0] * dd[0] + dd[1] * dd[1]) + dd[2] * dd[2];
 }
 
-// One thread per point: the closest point on the winning face again, in float64 from the float32 corners
-// (the loop's float32 distance only chose the face), so that the weights are those of the closest point
-// to rounding, thin faces included.  weights = the barycentric weights over the face's corners, rounded
-// once; dist2 = |p - (w0 a + w1 b + w2 c)|^2, formed in float64 before the weights are rounded and
-// rounded once (pm_closest64 has the rules).  grid: (ceil(N / 256), B).
-__global__ __launch_bounds__(PL_BLOCK) void k_point_face_finish(const float* __restrict__ points, long long p_stride,
-                                                                const float* __restrict__ vertices, const int32_t* __restrict__ faces,
-                                                                const int32_t* __restrict__ nearest, int N, int V,
-                                                                float* __restrict__ dist2, int32_t* __restrict__ face,
-                                                                float* __restrict__ weights) {
-    const int i = blockIdx.x * PL_BLOCK + threadIdx.x, b = blockIdx.y;
-    if (i >= N) return;
-    const long long n = (long long)b * N + i;
-    const int f = nearest[n];
+// The finish of both directions, one thread per (item, query): the closest point of the pair's face to the
+// pair's point again, in float64 from the float32 values (the loop's float32 distance only chose the target), so
+// that the weights are those of the closest point to rounding, thin faces included.  FaceQuery: the queries are
+// the faces and nearest [B, F] holds points ("k_face_point_finish"); else the queries are the points and nearest
+// [B, N] holds faces ("k_point_face_finish").  weights = the barycentric weights over the face's corners,
+// rounded once; dist2 = |p - (w0 a + w1 b + w2 c)|^2, formed in float64 before the weights are rounded and
+// rounded once (pm_closest64 has the rules); index = nearest.  Each of the three may be null.
+// grid: (ceil(queries / 256), B).
+template <bool FaceQuery>
+__global__ __launch_bounds__(PL_BLOCK) void k_pair_finish(const float* __restrict__ points, long long p_stride,
+                                                          const float* __restrict__ vertices, const int32_t* __restrict__ faces,
+                                                          const int32_t* __restrict__ nearest, int N, int V, int F,
+                                                          float* __restrict__ dist2, int32_t* __restrict__ index,
+                                                          float* __restrict__ weights) {
+    const int nq = FaceQuery ? F : N;
+    const int q = blockIdx.x * PL_BLOCK + threadIdx.x, b = blockIdx.y;
+    if (q >= nq) return;
+    const long long n = (long long)b * nq + q;
+    const int t = nearest[n];
+    const int i = FaceQuery ? t : q, f = FaceQuery ? q : t;
     const float* p = points + (long long)b * p_stride + (long long)i * 3;
     const float* vb = vertices + (long long)b * V * 3;
     const int i0 = faces[3 * (long long)f], i1 = faces[3 * (long long)f + 1], i2 = faces[3 * (long long)f + 2];
-    const float* pa = vb + (long long)i0 * 3;
-    const float* pb = vb + (long long)i1 * 3;
-    const float* pc = vb + (long long)i2 * 3;
     double w[3];
-    const double d2 = pm_closest64(p, i0, i1, i2, pa, pb, pc, w);
+    const double d2 = pm_closest64(p, i0, i1, i2, vb + (long long)i0 * 3, vb + (long long)i1 * 3, vb + (long long)i2 * 3, w);
     if (dist2) dist2[n] = (float)d2;
-    if (face) face[n] = f;
+    if (index) index[n] = t;
     if (weights) weights[n * 3] = (float)w[0], weights[n * 3 + 1] = (float)w[1], weights[n * 3 + 2] = (float)w[2];
+}
+
+// The gradient term of both directions, s (p - c) of the pair (point p, face f of the mesh vb) saved as row n:
+// c = (w0 a + w1 b) + w2 c of the saved weights, which w takes.
+__device__ __forceinline__ void pm_face_term(const float* __restrict__ p, const float* __restrict__ vb, const int32_t* __restrict__ faces,
+                                             const float* __restrict__ weights, long long n, int f, float s, float* g, float* w) {
+    const float* pa = vb + (long long)faces[3 * (long long)f] * 3;
+    const float* pb = vb + (long long)faces[3 * (long long)f + 1] * 3;
+    const float* pc = vb + (long long)faces[3 * (long long)f + 2] * 3;
+    w[0] = weights[n * 3], w[1] = weights[n * 3 + 1], w[2] = weights[n * 3 + 2];
+#pragma unroll
+    for (int k = 0; k < 3; k++) g[k] = s * (p[k] - ((w[0] * pa[k] + w[1] * pb[k]) + w[2] * pc[k]));
 }
 
 // One thread per point: c = w0 a + w1 b + w2 c of the saved face and weights, d = p - c,
@@ -290,16 +309,9 @@ __global__ __launch_bounds__(PL_BLOCK) void k_point_mesh_bwd(const float* __rest
     const long long n = (long long)b * N + i;
     const int f = face[n];
     const float* p = points + (long long)b * p_stride + (long long)i * 3;
-    const float* vb = vertices + (long long)b * V * 3;
     const int id[3] = {faces[3 * (long long)f], faces[3 * (long long)f + 1], faces[3 * (long long)f + 2]};
-    const float* pa = vb + (long long)id[0] * 3;
-    const float* pb = vb + (long long)id[1] * 3;
-    const float* pc = vb + (long long)id[2] * 3;
-    const float w[3] = {weights[n * 3], weights[n * 3 + 1], weights[n * 3 + 2]};
-    const float s = grad_loss[b] * (2.f / (float)N);
-    float g[3];
-#pragma unroll
-    for (int k = 0; k < 3; k++) g[k] = s * (p[k] - ((w[0] * pa[k] + w[1] * pb[k]) + w[2] * pc[k]));
+    float g[3], w[3];
+    pm_face_term(p, vertices + (long long)b * V * 3, faces, weights, n, f, grad_loss[b] * (2.f / (float)N), g, w);
     if (grad_points) {
 #pragma unroll
         for (int k = 0; k < 3; k++) grad_points[n * 3 + k] = g[k];

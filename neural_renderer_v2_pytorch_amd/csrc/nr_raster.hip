@@ -914,6 +914,15 @@ size_t nr_chamfer_workspace_bytes(int batch_size, int num_x, int num_y, int dire
            ((directions & NR_CHAMFER_Y_TO_X) ? chamfer_layout(batch_size, num_y, num_x).total : 0);
 }
 
+// The split path's tail, shared by every nearest-neighbour launch: a query's nsplit partials to the final arrays
+// (k_chamfer_combine).  One range wrote there itself.
+static int combine_split(const float* part_d2, const int32_t* part_index, int B, int nq, int nsplit, float* dist2, int32_t* index,
+                         hipStream_t st) {
+    if (nsplit == 1) return NR_OK;
+    nr_launch(k_chamfer_combine, grid_1d(nq, PL_BLOCK, B), dim3(PL_BLOCK), 0, st, part_d2, part_index, nq, nsplit, dist2, index);
+    return check_launch("k_chamfer_combine");
+}
+
 int nr_chamfer_forward(const float* x, const float* y, long long y_batch_stride, int batch_size, int num_x, int num_y,
                        int directions, int32_t* index_xy, int32_t* index_yx, float* dist2_xy, float* dist2_yx, float* loss,
                        void* workspace, size_t workspace_bytes, void* stream) {
@@ -963,10 +972,7 @@ int nr_chamfer_forward(const float* x, const float* y, long long y_batch_stride,
     e = check_launch("k_chamfer_nn");
     if (e) return e;
     for (int k = 0; k < nd; k++) {
-        if (d[k].nsplit == 1) continue;
-        nr_launch(k_chamfer_combine, grid_1d(d[k].nq, PL_BLOCK, B), dim3(PL_BLOCK), 0, st, (const float*)d[k].dist2,
-                  (const int32_t*)d[k].index, d[k].nq, d[k].nsplit, fin_d[k], fin_j[k]);
-        e = check_launch("k_chamfer_combine");
+        e = combine_split(d[k].dist2, d[k].index, B, d[k].nq, d[k].nsplit, fin_d[k], fin_j[k], st);
         if (e) return e;
     }
     if (!loss) return NR_OK;
@@ -1057,36 +1063,42 @@ int nr_sample_points_backward(const int32_t* faces, const int32_t* face, const f
     return check_launch("k_sample_points_bwd");
 }
 
-// ---- point-to-surface distance (nr_point_mesh.h) ----
-static int validate_point_mesh(int B, int N, int V, int F) {
+// ---- point-to-surface and face-to-scan distance (nr_point_mesh.h, nr_face_point.h): one path, a PairDir each ----
+// What every forward and backward of a direction starts with: the sizes and the stride; then, with nothing to
+// do (B == 0, or nothing wanted), NR_OK and *go false: no pointer is needed; then the three inputs.
+static int pair_begin(const PairDir& dir, int B, int N, int V, int F, long long points_batch_stride, bool wanted, const void* points,
+                      const void* vertices, const void* faces, bool* go) {
+    *go = false;
     if (B < 0) return fail(NR_ERR_ARGS, "bad batch size B=%d", B);
     if (N <= 0 || F <= 0 || V <= 0) return fail(NR_ERR_ARGS, "empty input N=%d F=%d V=%d (each must be at least 1)", N, F, V);
     if (B > 65535) return fail(NR_ERR_ARGS, "too many items B=%d (at most 65535)", B);
-    if ((long long)B * N > INT_MAX - 4096 || (long long)B * F > INT_MAX || (long long)B * V > INT_MAX / 3)
+    if ((long long)B * dir.queries(N, F) > INT_MAX - 4096 || (long long)B * dir.targets(N, F) > INT_MAX ||
+        (long long)B * V > INT_MAX / 3)
         return fail(NR_ERR_ARGS, "too many points, faces or vertices B=%d N=%d F=%d V=%d", B, N, F, V);
+    if (points_batch_stride < 0) return fail(NR_ERR_ARGS, "negative points batch stride");
+    if (B == 0 || !wanted) return NR_OK;
+    if (!points || !vertices || !faces) return fail(NR_ERR_ARGS, "null points, vertices or faces");
+    *go = true;
     return NR_OK;
 }
 
-size_t nr_point_mesh_workspace_bytes(int batch_size, int num_points, int num_faces) {
-    if (batch_size <= 0 || num_points <= 0 || num_faces <= 0) return 0;
-    return point_mesh_layout(batch_size, num_points, num_faces).total;
+static size_t pair_workspace_bytes(const PairDir& dir, int B, int N, int F) {
+    return B <= 0 || N <= 0 || F <= 0 ? 0 : pair_layout(dir, B, N, F).total;
 }
 
-int nr_point_mesh_forward(const float* points, long long points_batch_stride, const float* vertices, const int32_t* faces,
-                          int batch_size, int num_points, int num_vertices, int num_faces, float* dist2, int32_t* face,
-                          float* weights, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
-    const int B = batch_size, N = num_points, V = num_vertices, F = num_faces;
-    int e = validate_point_mesh(B, N, V, F);
-    if (e) return e;
-    if (points_batch_stride < 0) return fail(NR_ERR_ARGS, "negative points batch stride");
-    if (B == 0) return NR_OK;
-    if (!points || !vertices || !faces) return fail(NR_ERR_ARGS, "null points, vertices or faces");
-    if (!dist2 && !face && !weights && !loss) return fail(NR_ERR_ARGS, "no output asked for");
-    if (!workspace || workspace_bytes < nr_point_mesh_workspace_bytes(B, N, F))
-        return fail(NR_ERR_ARGS, "point_mesh workspace missing or too small");
+// records, the direction's nearest-neighbour loop, the combine of a split launch, the finish, the loss
+static int pair_forward(const PairDir& dir, const float* points, long long points_batch_stride, const float* vertices,
+                        const int32_t* faces, int B, int N, int V, int F, float* dist2, int32_t* index, float* weights, float* loss,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    bool go;
+    int e = pair_begin(dir, B, N, V, F, points_batch_stride, true, points, vertices, faces, &go);
+    if (e || !go) return e;
+    if (!dist2 && !index && !weights && !loss) return fail(NR_ERR_ARGS, "no output asked for");
+    const PairLayout wl = pair_layout(dir, B, N, F);
+    if (!workspace || workspace_bytes < wl.total) return fail(NR_ERR_ARGS, "%s workspace missing or too small", dir.name);
     hipStream_t st = (hipStream_t)stream;
-    const PointMeshLayout wl = point_mesh_layout(B, N, F);
     const SplitPlan p = wl.plan;
+    const int nq = dir.queries(N, F);
     char* ws = (char*)workspace;
     float* records = (float*)(ws + wl.records);
     int32_t* nearest = (int32_t*)(ws + wl.nearest);
@@ -1095,42 +1107,47 @@ int nr_point_mesh_forward(const float* points, long long points_batch_stride, co
     nr_launch(k_point_face_records, grid_1d(F, PL_BLOCK, B), dim3(PL_BLOCK), 0, st, vertices, faces, V, F, records);
     e = check_launch("k_point_face_records");
     if (e) return e;
-    PmArgs d;
+    PairArgs d;
     d.points = points, d.p_stride = points_batch_stride, d.records = records, d.N = N, d.F = F, d.nsplit = p.nsplit;
     if (p.nsplit > 1) {
-        d.dist2 = (float*)(ws + wl.part_d2), d.face = (int32_t*)(ws + wl.part_f);
+        d.dist2 = (float*)(ws + wl.part_d2), d.index = (int32_t*)(ws + wl.part_index);
     } else {
-        d.dist2 = loop_d2, d.face = nearest;
+        d.dist2 = loop_d2, d.index = nearest;
     }
-    nr_launch(k_point_face_nn, dim3((unsigned)(p.nqb * p.nsplit), (unsigned)B), dim3(PL_BLOCK), 0, st, d);
-    g_last_point_mesh.store(LaunchRec{PL_BLOCK, p.nsplit > 1 ? NR_LAUNCH_SPLIT_FACES : 0});
-    e = check_launch("k_point_face_nn");
+    nr_launch(dir.nn, dim3((unsigned)(p.nqb * p.nsplit), (unsigned)B), dim3(PL_BLOCK), 0, st, d);
+    dir.slot->store(LaunchRec{PL_BLOCK, p.nsplit > 1 ? dir.split_flag : 0});
+    e = check_launch(dir.nn_name);
     if (e) return e;
-    const dim3 per_point = grid_1d(N, PL_BLOCK, B);
-    if (p.nsplit > 1) {
-        nr_launch(k_chamfer_combine, per_point, dim3(PL_BLOCK), 0, st, (const float*)d.dist2, (const int32_t*)d.face, N, p.nsplit,
-                  loop_d2, nearest);
-        e = check_launch("k_chamfer_combine");
-        if (e) return e;
-    }
+    e = combine_split(d.dist2, d.index, B, nq, p.nsplit, loop_d2, nearest, st);
+    if (e) return e;
     const bool need_d2 = dist2 || loss;
-    nr_launch(k_point_face_finish, per_point, dim3(PL_BLOCK), 0, st, points, points_batch_stride, vertices, faces,
-              (const int32_t*)nearest, N, V, need_d2 ? fin_d2 : (float*)nullptr, face, weights);
-    e = check_launch("k_point_face_finish");
+    nr_launch(dir.finish, grid_1d(nq, PL_BLOCK, B), dim3(PL_BLOCK), 0, st, points, points_batch_stride, vertices, faces,
+              (const int32_t*)nearest, N, V, F, need_d2 ? fin_d2 : (float*)nullptr, index, weights);
+    e = check_launch(dir.finish_name);
     if (e || !loss) return e;
-    nr_launch(k_chamfer_sum, dim3((unsigned)B), dim3(PL_WIDE), 0, st, (const float*)fin_d2, N, (const float*)nullptr, 0, loss);
+    nr_launch(k_chamfer_sum, dim3((unsigned)B), dim3(PL_WIDE), 0, st, (const float*)fin_d2, nq, (const float*)nullptr, 0, loss);
     return check_launch("k_chamfer_sum");
+}
+
+size_t nr_point_mesh_workspace_bytes(int batch_size, int num_points, int num_faces) {
+    return pair_workspace_bytes(POINT_FACE, batch_size, num_points, num_faces);
+}
+
+int nr_point_mesh_forward(const float* points, long long points_batch_stride, const float* vertices, const int32_t* faces,
+                          int batch_size, int num_points, int num_vertices, int num_faces, float* dist2, int32_t* face,
+                          float* weights, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+    return pair_forward(POINT_FACE, points, points_batch_stride, vertices, faces, batch_size, num_points, num_vertices, num_faces,
+                        dist2, face, weights, loss, workspace, workspace_bytes, stream);
 }
 
 int nr_point_mesh_backward(const float* points, long long points_batch_stride, const float* vertices, const int32_t* faces,
                            const int32_t* face, const float* weights, const float* grad_loss, int batch_size, int num_points,
                            int num_vertices, int num_faces, float* grad_points, float* grad_vertices, void* stream) {
     const int B = batch_size, N = num_points, V = num_vertices, F = num_faces;
-    int e = validate_point_mesh(B, N, V, F);
-    if (e) return e;
-    if (points_batch_stride < 0) return fail(NR_ERR_ARGS, "negative points batch stride");
-    if (B == 0 || (!grad_points && !grad_vertices)) return NR_OK;
-    if (!points || !vertices || !faces || !face || !weights || !grad_loss) return fail(NR_ERR_ARGS, "null pointer");
+    bool go;
+    int e = pair_begin(POINT_FACE, B, N, V, F, points_batch_stride, grad_points || grad_vertices, points, vertices, faces, &go);
+    if (e || !go) return e;
+    if (!face || !weights || !grad_loss) return fail(NR_ERR_ARGS, "null pointer");
     hipStream_t st = (hipStream_t)stream;
     if (grad_vertices && !zero_async(grad_vertices, (size_t)B * V * 3 * 4, st, &e)) return e;
     nr_launch(k_point_mesh_bwd, grid_1d(N, PL_BLOCK, B), dim3(PL_BLOCK), 0, st, points,
@@ -1138,69 +1155,15 @@ int nr_point_mesh_backward(const float* points, long long points_batch_stride, c
     return check_launch("k_point_mesh_bwd");
 }
 
-// ---- face-to-scan distance (nr_face_point.h) ----
-static int validate_face_point(int B, int N, int V, int F) {
-    if (B < 0) return fail(NR_ERR_ARGS, "bad batch size B=%d", B);
-    if (N <= 0 || F <= 0 || V <= 0) return fail(NR_ERR_ARGS, "empty input N=%d F=%d V=%d (each must be at least 1)", N, F, V);
-    if (B > 65535) return fail(NR_ERR_ARGS, "too many items B=%d (at most 65535)", B);
-    if ((long long)B * F > INT_MAX - 4096 || (long long)B * N > INT_MAX || (long long)B * V > INT_MAX / 3)
-        return fail(NR_ERR_ARGS, "too many points, faces or vertices B=%d N=%d F=%d V=%d", B, N, F, V);
-    return NR_OK;
-}
-
 size_t nr_face_point_workspace_bytes(int batch_size, int num_points, int num_faces) {
-    if (batch_size <= 0 || num_points <= 0 || num_faces <= 0) return 0;
-    return face_point_layout(batch_size, num_points, num_faces).total;
+    return pair_workspace_bytes(FACE_POINT, batch_size, num_points, num_faces);
 }
 
 int nr_face_point_forward(const float* points, long long points_batch_stride, const float* vertices, const int32_t* faces,
                           int batch_size, int num_points, int num_vertices, int num_faces, float* dist2, int32_t* point,
                           float* weights, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
-    const int B = batch_size, N = num_points, V = num_vertices, F = num_faces;
-    int e = validate_face_point(B, N, V, F);
-    if (e) return e;
-    if (points_batch_stride < 0) return fail(NR_ERR_ARGS, "negative points batch stride");
-    if (B == 0) return NR_OK;
-    if (!points || !vertices || !faces) return fail(NR_ERR_ARGS, "null points, vertices or faces");
-    if (!dist2 && !point && !weights && !loss) return fail(NR_ERR_ARGS, "no output asked for");
-    if (!workspace || workspace_bytes < nr_face_point_workspace_bytes(B, N, F))
-        return fail(NR_ERR_ARGS, "face_point workspace missing or too small");
-    hipStream_t st = (hipStream_t)stream;
-    const FacePointLayout wl = face_point_layout(B, N, F);
-    const SplitPlan p = wl.plan;
-    char* ws = (char*)workspace;
-    float* records = (float*)(ws + wl.records);
-    int32_t* nearest = (int32_t*)(ws + wl.nearest);
-    float* loop_d2 = (float*)(ws + wl.loop_d2);
-    float* fin_d2 = dist2 ? dist2 : (float*)(ws + wl.fin_d2);
-    const dim3 per_face = grid_1d(F, PL_BLOCK, B);
-    nr_launch(k_point_face_records, per_face, dim3(PL_BLOCK), 0, st, vertices, faces, V, F, records);
-    e = check_launch("k_point_face_records");
-    if (e) return e;
-    FpArgs d;
-    d.points = points, d.p_stride = points_batch_stride, d.records = records, d.N = N, d.F = F, d.nsplit = p.nsplit;
-    if (p.nsplit > 1) {
-        d.dist2 = (float*)(ws + wl.part_d2), d.point = (int32_t*)(ws + wl.part_i);
-    } else {
-        d.dist2 = loop_d2, d.point = nearest;
-    }
-    nr_launch(k_face_point_nn, dim3((unsigned)(p.nqb * p.nsplit), (unsigned)B), dim3(PL_BLOCK), 0, st, d);
-    g_last_face_point.store(LaunchRec{PL_BLOCK, p.nsplit > 1 ? NR_LAUNCH_SPLIT_POINTS : 0});
-    e = check_launch("k_face_point_nn");
-    if (e) return e;
-    if (p.nsplit > 1) {
-        nr_launch(k_chamfer_combine, per_face, dim3(PL_BLOCK), 0, st, (const float*)d.dist2, (const int32_t*)d.point, F, p.nsplit,
-                  loop_d2, nearest);
-        e = check_launch("k_chamfer_combine");
-        if (e) return e;
-    }
-    const bool need_d2 = dist2 || loss;
-    nr_launch(k_face_point_finish, per_face, dim3(PL_BLOCK), 0, st, points, points_batch_stride, vertices, faces,
-              (const int32_t*)nearest, V, F, need_d2 ? fin_d2 : (float*)nullptr, point, weights);
-    e = check_launch("k_face_point_finish");
-    if (e || !loss) return e;
-    nr_launch(k_chamfer_sum, dim3((unsigned)B), dim3(PL_WIDE), 0, st, (const float*)fin_d2, F, (const float*)nullptr, 0, loss);
-    return check_launch("k_chamfer_sum");
+    return pair_forward(FACE_POINT, points, points_batch_stride, vertices, faces, batch_size, num_points, num_vertices, num_faces,
+                        dist2, point, weights, loss, workspace, workspace_bytes, stream);
 }
 
 int nr_face_point_backward(const float* points, long long points_batch_stride, const float* vertices, const int32_t* faces,
@@ -1208,11 +1171,10 @@ int nr_face_point_backward(const float* points, long long points_batch_stride, c
                            const float* grad_loss, int batch_size, int num_points, int num_vertices, int num_faces,
                            float* grad_points, float* grad_vertices, void* stream) {
     const int B = batch_size, N = num_points, V = num_vertices, F = num_faces;
-    int e = validate_face_point(B, N, V, F);
-    if (e) return e;
-    if (points_batch_stride < 0) return fail(NR_ERR_ARGS, "negative points batch stride");
-    if (B == 0 || (!grad_points && !grad_vertices)) return NR_OK;
-    if (!points || !vertices || !faces || !point || !weights || !grad_loss) return fail(NR_ERR_ARGS, "null pointer");
+    bool go;
+    int e = pair_begin(FACE_POINT, B, N, V, F, points_batch_stride, grad_points || grad_vertices, points, vertices, faces, &go);
+    if (e || !go) return e;
+    if (!point || !weights || !grad_loss) return fail(NR_ERR_ARGS, "null pointer");
     if (grad_vertices && (!corner_offsets || !corner_index)) return fail(NR_ERR_ARGS, "grad_vertices needs the corner CSR lists");
     hipStream_t st = (hipStream_t)stream;
     if (grad_vertices) {

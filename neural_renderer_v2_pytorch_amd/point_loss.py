@@ -480,32 +480,47 @@ def _points_stride(p):
     return 0 if p.ndim == 2 or p.stride(0) == 0 else p.shape[1] * 3
 
 
-def _point_mesh_launch(p, v, f, want_loss):
-    """p as _dense_y gives it, v [B, V, 3] contiguous, f [F, 3] int32 -> (loss or None, dist2, face, weights)."""
+# The two directions of the fused path: the entry points' prefix (nr_<abi>_workspace_bytes / _forward / _backward,
+# include/nr_raster.h) and whether the faces are the queries.  Everything below that differs between them reads
+# it from here.
+_POINT_FACE = ("nr_point_mesh", False)  # for every point its nearest face
+_FACE_POINT = ("nr_face_point", True)   # for every face its nearest point
+
+
+def _pair_launch(p, v, f, direction, want_loss):
+    """p as _dense_y gives it, v [B, V, 3] contiguous, f [F, 3] int32 -> (loss or None, dist2, index, weights), a row
+    per query: per point (index: its face) in _POINT_FACE, per face (index: its point) in _FACE_POINT."""
+    abi, face_query = direction
     B, N, V, F = v.shape[0], p.shape[-2], v.shape[1], f.shape[0]
+    Q = F if face_query else N
     dev = v.device
     L = _lib.lib()
-    dist2 = torch.empty((B, N), dtype=torch.float32, device=dev)
-    face = torch.empty((B, N), dtype=torch.int32, device=dev)
-    weights = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    dist2 = torch.empty((B, Q), dtype=torch.float32, device=dev)
+    index = torch.empty((B, Q), dtype=torch.int32, device=dev)
+    weights = torch.empty((B, Q, 3), dtype=torch.float32, device=dev)
     loss = torch.empty(B, dtype=torch.float32, device=dev) if want_loss else None
-    ws = torch.empty(L.nr_point_mesh_workspace_bytes(B, N, F), dtype=torch.uint8, device=dev)
+    ws = torch.empty(getattr(L, abi + "_workspace_bytes")(B, N, F), dtype=torch.uint8, device=dev)
     with _lib.on_device(dev):
-        _lib.check(L.nr_point_mesh_forward(_lib.ptr(p), _points_stride(p), _lib.ptr(v), _lib.ptr(f), B, N, V, F, _lib.ptr(dist2),
-                                           _lib.ptr(face), _lib.ptr(weights), _lib.ptr(loss), _lib.ptr(ws), ws.numel(),
-                                           _lib.stream_of(v)), "nr_point_mesh_forward")
-    return loss, dist2, face, weights
+        _lib.check(getattr(L, abi + "_forward")(_lib.ptr(p), _points_stride(p), _lib.ptr(v), _lib.ptr(f), B, N, V, F, _lib.ptr(dist2),
+                                                _lib.ptr(index), _lib.ptr(weights), _lib.ptr(loss), _lib.ptr(ws), ws.numel(),
+                                                _lib.stream_of(v)), abi + "_forward")
+    return loss, dist2, index, weights
 
 
-class PointMeshFunction(torch.autograd.Function):
-    """points as _dense_y gives them, vertices [B, V, 3] float32 contiguous on the GPU, faces [F, 3] int32 ->
-    loss [B]; saves the chosen faces and the weights (and the inputs, which the backward reads again)."""
+class PairDistanceFunction(torch.autograd.Function):
+    """points as _dense_y gives them, vertices [B, V, 3] float32 contiguous on the GPU, faces [F, 3] int32, a direction
+    -> loss [B]; saves the chosen index and the weights (and the inputs, which the backward reads again).  The
+    corner lists of _FACE_POINT's vertex gather are looked up in the forward (cached per faces tensor), so the
+    backward does no host work."""
 
     @staticmethod
-    def forward(ctx, points, vertices, faces):
-        loss, _, face, weights = _point_mesh_launch(points, vertices, faces, True)
+    def forward(ctx, points, vertices, faces, direction):
+        loss, _, index, weights = _pair_launch(points, vertices, faces, direction, True)
+        ctx.direction = direction
         if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            ctx.save_for_backward(points, vertices, faces, face, weights)
+            ctx.save_for_backward(points, vertices, faces, index, weights)
+            if direction[1]:
+                ctx.corners = vertex_adjacency(faces, vertices.shape[1]) if ctx.needs_input_grad[1] else (None, None)
         return loss
 
     @staticmethod
@@ -513,19 +528,21 @@ class PointMeshFunction(torch.autograd.Function):
     def backward(ctx, grad_loss):
         need_p, need_v = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (need_p or need_v):
-            return None, None, None
-        p, v, f, face, weights = ctx.saved_tensors
+            return None, None, None, None
+        abi, face_query = ctx.direction
+        p, v, f, index, weights = ctx.saved_tensors
         B, N, V = v.shape[0], p.shape[-2], v.shape[1]
         if need_p and p.ndim == 2:
             raise RuntimeError("shared points that take a gradient must be passed batch-expanded")
         g = grad_loss.to(torch.float32).contiguous()
         gp = torch.empty((B, N, 3), dtype=torch.float32, device=v.device) if need_p else None
         gv = torch.empty_like(v) if need_v else None
+        corners = [_lib.ptr(c) for c in ctx.corners] if face_query else []
         with _lib.on_device(v.device):
-            _lib.check(_lib.lib().nr_point_mesh_backward(_lib.ptr(p), _points_stride(p), _lib.ptr(v), _lib.ptr(f), _lib.ptr(face),
-                                                         _lib.ptr(weights), _lib.ptr(g), B, N, V, f.shape[0], _lib.ptr(gp),
-                                                         _lib.ptr(gv), _lib.stream_of(v)), "nr_point_mesh_backward")
-        return gp, gv, None
+            _lib.check(getattr(_lib.lib(), abi + "_backward")(_lib.ptr(p), _points_stride(p), _lib.ptr(v), _lib.ptr(f), *corners,
+                                                              _lib.ptr(index), _lib.ptr(weights), _lib.ptr(g), B, N, V, f.shape[0],
+                                                              _lib.ptr(gp), _lib.ptr(gv), _lib.stream_of(v)), abi + "_backward")
+        return gp, gv, None, None
 
 
 def point_mesh_distance(points, vertices, faces, average=False):
@@ -548,7 +565,7 @@ def point_mesh_distance(points, vertices, faces, average=False):
     p, v, f, single = _prepare_point_mesh(points, vertices, faces)
     if p.ndim == 2 and p.requires_grad and torch.is_grad_enabled():
         p = p[None].expand(v.shape[0], -1, -1)
-    return _finish(PointMeshFunction.apply(_dense_y(p), v.contiguous(), f), single, average)
+    return _finish(PairDistanceFunction.apply(_dense_y(p), v.contiguous(), f, _POINT_FACE), single, average)
 
 
 def closest_points_on_mesh(points, vertices, faces):
@@ -562,7 +579,7 @@ def closest_points_on_mesh(points, vertices, faces):
         return closest_points_on_mesh_torch(points, vertices, faces)
     p, v, f, single = _prepare_point_mesh(points, vertices, faces)
     with torch.no_grad():
-        _, dist2, face, weights = _point_mesh_launch(_dense_y(p.detach()), v.detach().contiguous(), f, False)
+        _, dist2, face, weights = _pair_launch(_dense_y(p.detach()), v.detach().contiguous(), f, _POINT_FACE, False)
     return (dist2[0], face[0], weights[0]) if single else (dist2, face, weights)
 
 
@@ -618,59 +635,6 @@ def mesh_point_distance_torch(vertices, faces, points, average=False, point=None
     return _finish(dist2.mean(1), single, average)
 
 
-def _face_point_launch(p, v, f, want_loss):
-    """p as _dense_y gives it, v [B, V, 3] contiguous, f [F, 3] int32 -> (loss or None, dist2, point, weights)."""
-    B, N, V, F = v.shape[0], p.shape[-2], v.shape[1], f.shape[0]
-    dev = v.device
-    L = _lib.lib()
-    dist2 = torch.empty((B, F), dtype=torch.float32, device=dev)
-    point = torch.empty((B, F), dtype=torch.int32, device=dev)
-    weights = torch.empty((B, F, 3), dtype=torch.float32, device=dev)
-    loss = torch.empty(B, dtype=torch.float32, device=dev) if want_loss else None
-    ws = torch.empty(L.nr_face_point_workspace_bytes(B, N, F), dtype=torch.uint8, device=dev)
-    with _lib.on_device(dev):
-        _lib.check(L.nr_face_point_forward(_lib.ptr(p), _points_stride(p), _lib.ptr(v), _lib.ptr(f), B, N, V, F, _lib.ptr(dist2),
-                                           _lib.ptr(point), _lib.ptr(weights), _lib.ptr(loss), _lib.ptr(ws), ws.numel(),
-                                           _lib.stream_of(v)), "nr_face_point_forward")
-    return loss, dist2, point, weights
-
-
-class MeshPointFunction(torch.autograd.Function):
-    """vertices [B, V, 3] float32 contiguous on the GPU, points as _dense_y gives them, faces [F, 3] int32 ->
-    loss [B]; saves the chosen points and the weights (and the inputs, which the backward reads again).  The
-    corner lists of the vertex gather are looked up in the forward (cached per faces tensor), so the backward
-    does no host work."""
-
-    @staticmethod
-    def forward(ctx, vertices, points, faces):
-        loss, _, point, weights = _face_point_launch(points, vertices, faces, True)
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            ctx.save_for_backward(points, vertices, faces, point, weights)
-            ctx.corners = vertex_adjacency(faces, vertices.shape[1]) if ctx.needs_input_grad[0] else (None, None)
-        return loss
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, grad_loss):
-        need_v, need_p = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_p or need_v):
-            return None, None, None
-        p, v, f, point, weights = ctx.saved_tensors
-        B, N, V = v.shape[0], p.shape[-2], v.shape[1]
-        if need_p and p.ndim == 2:
-            raise RuntimeError("shared points that take a gradient must be passed batch-expanded")
-        g = grad_loss.to(torch.float32).contiguous()
-        gp = torch.empty((B, N, 3), dtype=torch.float32, device=v.device) if need_p else None
-        gv = torch.empty_like(v) if need_v else None
-        offsets, index = ctx.corners
-        with _lib.on_device(v.device):
-            _lib.check(_lib.lib().nr_face_point_backward(_lib.ptr(p), _points_stride(p), _lib.ptr(v), _lib.ptr(f), _lib.ptr(offsets),
-                                                         _lib.ptr(index), _lib.ptr(point), _lib.ptr(weights), _lib.ptr(g), B, N, V,
-                                                         f.shape[0], _lib.ptr(gp), _lib.ptr(gv), _lib.stream_of(v)),
-                       "nr_face_point_backward")
-        return gv, gp, None
-
-
 def mesh_point_distance(vertices, faces, points, average=False):
     """(1/F) sum_f min_i dist^2(p_i, T_f) per item, T_f the triangle f as a closed set: the mean over the faces of
     the squared distance from the face to its nearest point, the term that keeps a mesh from growing surface
@@ -693,7 +657,7 @@ def mesh_point_distance(vertices, faces, points, average=False):
     p, v, f, single = _prepare_point_mesh(points, vertices, faces)
     if p.ndim == 2 and p.requires_grad and torch.is_grad_enabled():
         p = p[None].expand(v.shape[0], -1, -1)
-    return _finish(MeshPointFunction.apply(v.contiguous(), _dense_y(p), f), single, average)
+    return _finish(PairDistanceFunction.apply(_dense_y(p), v.contiguous(), f, _FACE_POINT), single, average)
 
 
 def closest_points_to_faces(vertices, faces, points):
@@ -705,41 +669,41 @@ def closest_points_to_faces(vertices, faces, points):
         return closest_points_to_faces_torch(vertices, faces, points)
     p, v, f, single = _prepare_point_mesh(points, vertices, faces)
     with torch.no_grad():
-        _, dist2, point, weights = _face_point_launch(_dense_y(p.detach()), v.detach().contiguous(), f, False)
+        _, dist2, point, weights = _pair_launch(_dense_y(p.detach()), v.detach().contiguous(), f, _FACE_POINT, False)
     return (dist2[0], point[0], weights[0]) if single else (dist2, point, weights)
 
 
-class MeshPointLoss(torch.nn.Module):
+class _PointSetLoss(torch.nn.Module):
+    """A distance between the mesh given to forward and an optional fixed point set held by the module (a buffer: it
+    moves with .to()); forward(vertices, faces) uses it, forward(vertices, faces, points) the given points."""
+
+    def __init__(self, points=None, average=False):
+        super().__init__()
+        self.register_buffer("points", None if points is None else torch.as_tensor(points).detach().clone())
+        self.average = average
+
+    def forward(self, vertices, faces, points=None):
+        points = self.points if points is None else points
+        if points is None:
+            raise ValueError("%s needs points: pass them, or construct the module with a point set" % type(self).__name__)
+        return self.distance(points, vertices, faces)
+
+
+class MeshPointLoss(_PointSetLoss):
     """mesh_point_distance from the mesh given to forward to an optional fixed point set held by the module (a
     buffer: it moves with .to()); forward(vertices, faces) uses it, forward(vertices, faces, points) the given
     points."""
 
-    def __init__(self, points=None, average=False):
-        super().__init__()
-        self.register_buffer("points", None if points is None else torch.as_tensor(points).detach().clone())
-        self.average = average
-
-    def forward(self, vertices, faces, points=None):
-        points = self.points if points is None else points
-        if points is None:
-            raise ValueError("MeshPointLoss needs points: pass them, or construct the module with a point set")
+    def distance(self, points, vertices, faces):
         return mesh_point_distance(vertices, faces, points, self.average)
 
 
-class PointMeshLoss(torch.nn.Module):
+class PointMeshLoss(_PointSetLoss):
     """point_mesh_distance from an optional fixed point set held by the module (a buffer: it moves with
     .to()) to the mesh given to forward; forward(vertices, faces) uses it, forward(vertices, faces, points)
     the given points."""
 
-    def __init__(self, points=None, average=False):
-        super().__init__()
-        self.register_buffer("points", None if points is None else torch.as_tensor(points).detach().clone())
-        self.average = average
-
-    def forward(self, vertices, faces, points=None):
-        points = self.points if points is None else points
-        if points is None:
-            raise ValueError("PointMeshLoss needs points: pass them, or construct the module with a point set")
+    def distance(self, points, vertices, faces):
         return point_mesh_distance(points, vertices, faces, self.average)
 
 

@@ -422,3 +422,30 @@ def test_abi_rejects_bad_arguments(dev):
     assert forward(B=0, points=None, vertices=None, faces=None, ws=None) == 0
     assert backward(B=0, points=None, vertices=None, faces=None) == 0
     assert backward(gp=None, gv=None, points=None) == 0
+
+
+def test_null_outputs_leave_the_others_unchanged(dev):
+    """nr_face_point_forward itself (the wrappers always ask for dist2, point and weights), unsplit with a partial last
+    block and split: the loss alone, then each of dist2, point and weights alone, is bit for bit what the call with
+    every output writes.  Each array starts at -1, which no result holds."""
+    L = _lib.lib()
+    for name in ("partial", "three_ranges"):
+        p, v, f, _ = case(name)
+        B, N, V, F = p.shape[0], p.shape[1], v.shape[1], f.shape[0]
+        pd, vd, fd = p.to(dev), v.to(dev), f.to(dev).int()
+        ws = torch.empty(L.nr_face_point_workspace_bytes(B, N, F), dtype=torch.uint8, device=dev)
+
+        def run(*want):
+            out = {"dist2": torch.full((B, F), -1., device=dev), "point": torch.full((B, F), -1, dtype=torch.int32, device=dev),
+                   "weights": torch.full((B, F, 3), -1., device=dev), "loss": torch.full((B,), -1., device=dev)}
+            ptrs = [_lib.ptr(out[k] if k in want else None) for k in ("dist2", "point", "weights", "loss")]
+            _lib.check(L.nr_face_point_forward(_lib.ptr(pd), N * 3, _lib.ptr(vd), _lib.ptr(fd), B, N, V, F, *ptrs, _lib.ptr(ws),
+                                               ws.numel(), _lib.stream_of(vd)), "nr_face_point_forward")
+            assert _lib.last_launch(KERNEL) == (256, SPLIT_FLAG if name in SPLIT else 0)
+            return out
+
+        full = run("dist2", "point", "weights", "loss")
+        assert float(full["dist2"].min()) >= 0 and int(full["point"].min()) >= 0 and float(full["weights"].min()) >= 0
+        assert float(full["loss"].min()) > 0
+        for only in ("loss", "dist2", "point", "weights"):
+            assert torch.equal(run(only)[only], full[only]), (name, only)

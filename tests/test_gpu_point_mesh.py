@@ -406,3 +406,30 @@ def test_non_finite_queries(dev, name):
     torch.cuda.synchronize()
     assert gp.shape == q.shape and gv.shape == v.shape
     assert torch.equal(gp[~hit], fused(p, v, f, g, dev)[1][~hit])
+
+
+def test_null_outputs_leave_the_others_unchanged(dev):
+    """nr_point_mesh_forward itself (the wrappers always ask for dist2, face and weights), unsplit with a partial last
+    block and split: the loss alone, then each of dist2, face and weights alone, is bit for bit what the call with
+    every output writes.  Each array starts at -1, which no result holds."""
+    L = _lib.lib()
+    for name in ("partial", "three_ranges"):
+        p, v, f, _, _ = case(name)
+        B, N, V, F = p.shape[0], p.shape[1], v.shape[1], f.shape[0]
+        pd, vd, fd = p.to(dev), v.to(dev), f.to(dev).int()
+        ws = torch.empty(L.nr_point_mesh_workspace_bytes(B, N, F), dtype=torch.uint8, device=dev)
+
+        def run(*want):
+            out = {"dist2": torch.full((B, N), -1., device=dev), "face": torch.full((B, N), -1, dtype=torch.int32, device=dev),
+                   "weights": torch.full((B, N, 3), -1., device=dev), "loss": torch.full((B,), -1., device=dev)}
+            ptrs = [_lib.ptr(out[k] if k in want else None) for k in ("dist2", "face", "weights", "loss")]
+            _lib.check(L.nr_point_mesh_forward(_lib.ptr(pd), N * 3, _lib.ptr(vd), _lib.ptr(fd), B, N, V, F, *ptrs, _lib.ptr(ws),
+                                               ws.numel(), _lib.stream_of(vd)), "nr_point_mesh_forward")
+            assert _lib.last_launch(KERNEL) == (256, _lib.NR_LAUNCH_SPLIT_FACES if name in SPLIT else 0)
+            return out
+
+        full = run("dist2", "face", "weights", "loss")
+        assert float(full["dist2"].min()) >= 0 and int(full["face"].min()) >= 0 and float(full["weights"].min()) >= 0
+        assert float(full["loss"].min()) > 0
+        for only in ("loss", "dist2", "face", "weights"):
+            assert torch.equal(run(only)[only], full[only]), (name, only)
