@@ -389,6 +389,42 @@ NR_API int nr_iou_loss_backward(const float* targets, long long target_stride, c
                                 int batch_size, int item_elems, const float* grad_loss, float* grad_images,
                                 void* stream);
 
+/* SSIM loss (image_loss.py ssim_loss; Wang et al. 2004): images [B, C, H, W] float32, item b being the
+ * C H W contiguous floats at images + b * image_stride; targets the same at target_stride (0 = shared).
+ * window: HOST array of window_size float32 weights g, window_size = 2R + 1 odd in 3..11 (read during the
+ * call, passed to the kernels by value); G = g (x) g, applied per channel.  padding NR_SSIM_SAME: zeros
+ * R pixels around the image, the map is H' x W' = H x W; NR_SSIM_VALID: no padding, H' x W' =
+ * (H - 2R) x (W - 2R), which must be at least 1 x 1.  Per map pixel, with x the image and t the target:
+ *   mu1 = G*x   mu2 = G*t   s11 = G*x^2 - mu1^2   s22 = G*t^2 - mu2^2   s12 = G*(x t) - mu1 mu2
+ *   n1 = 2 mu1 mu2 + c1   n2 = 2 s12 + c2   d1 = mu1^2 + mu2^2 + c1   d2 = s11 + s22 + c2
+ *   S = n1 n2 / (d1 d2)          loss_b = 1 - (sum of S over the item's C H' W' map pixels) / (C H' W')
+ * No variance clamp.  The forward with saved != NULL also writes three maps, saved [3][B][C][H'][W']:
+ *   Bm = -S / d2 (= dS / d G*x^2)      Cm = 2 n1 / (d1 d2) (= dS / d G*(x t))
+ *   A  = 2 mu2 n2 / (d1 d2) - 2 mu1 S / d1 - 2 mu1 Bm - mu2 Cm (= dS / d mu1)
+ * which with the inputs are all the backward reads (the maps zero outside H' x W', 'valid' maps sitting R
+ * pixels inside the image):
+ *   grad x(p) = -(g_b / (C H' W')) ((G*A)(p) + 2 x(p) (G*Bm)(p) + t(p) (G*Cm)(p))
+ * One block per 32 x 32 tile of one channel stages the tile and its R-pixel halo in LDS and filters rows,
+ * then columns; the filter taps are fused multiply-adds.  No float atomics: bitwise reproducible.
+ * Limits: C H W <= INT_MAX, B C ceil(H / 32) ceil(W / 32) <= INT_MAX (NR_ERR_ARGS otherwise).  With B == 0
+ * nothing is written; with C H W == 0 the losses are 0 (a fill on the stream) and no kernel is launched.
+ *
+ * Scratch bytes of a forward: the per-tile partial sums [B][C][tiles of the map]; no zero fill needed
+ * (0 for sizes the entry points reject). */
+enum { NR_SSIM_SAME = 0, NR_SSIM_VALID = 1 };
+NR_API size_t nr_ssim_loss_workspace_bytes(int batch_size, int channels, int height, int width, int window_size,
+                                           int padding);
+/* loss [B], fully written; saved NULL (no gradient wanted) or [3][B][C][H'][W'], fully written. */
+NR_API int nr_ssim_loss_forward(const float* images, long long image_stride, const float* targets,
+                                long long target_stride, int batch_size, int channels, int height, int width,
+                                int window_size, const float* window, float c1, float c2, int padding, float* loss,
+                                float* saved, void* workspace, size_t workspace_bytes, void* stream);
+/* grad_loss [B] -> grad_images [B, C H W] contiguous, fully written, from the forward's saved maps. */
+NR_API int nr_ssim_loss_backward(const float* images, long long image_stride, const float* targets,
+                                 long long target_stride, const float* saved, int batch_size, int channels,
+                                 int height, int width, int window_size, const float* window, int padding,
+                                 const float* grad_loss, float* grad_images, void* stream);
+
 /* Optimiser (optimizers.py): Adam over a list of float32 tensors, with the two rules of the reference's
  * optimizers.py:1-37: an element whose gradient is zero is left alone (skip_zero_grad), and each tensor
  * scales the rate by its own lr_scale (the reference's param.lr).  One call advances every listed

@@ -19,8 +19,8 @@ from .differentiation import differentiation
 from .camera import camera_transform, projection_transform
 from .mesh_loss import (FlattenLoss, LaplacianLoss, MeshTopology, flatten_loss, flatten_loss_torch, laplacian_loss,
                         laplacian_loss_torch, mesh_topology)
-from .image_loss import (HuberLoss, IoULoss, SquaredErrorLoss, huber_loss, huber_loss_torch, iou_loss, iou_loss_torch,
-                         squared_error_loss, squared_error_loss_torch)
+from .image_loss import (HuberLoss, IoULoss, SquaredErrorLoss, SSIMLoss, huber_loss, huber_loss_torch, iou_loss, iou_loss_torch,
+                         squared_error_loss, squared_error_loss_torch, ssim_loss, ssim_loss_torch)
 from .optimizers import Adam, adam_step_torch
 from .attributes import (NR_ATTR_MAX_CHANNELS, attributes_from_maps_torch, rasterize_attributes,
                          rasterize_attributes_torch)

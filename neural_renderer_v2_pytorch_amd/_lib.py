@@ -54,6 +54,8 @@ class NrRasterArgs(ctypes.Structure):
 NR_LIGHT_AMBIENT, NR_LIGHT_DIRECTIONAL, NR_LIGHT_SPECULAR, NR_LIGHT_FLOATS = 0, 1, 2, 8
 NR_CAMERA_NONE, NR_CAMERA_LOOK_AT, NR_CAMERA_LOOK = 0, 1, 2
 NR_LOSS_SQUARED, NR_LOSS_HUBER = 0, 1
+NR_SSIM_SAME, NR_SSIM_VALID = 0, 1
+NR_SSIM_TILE, NR_SSIM_MAX_WINDOW = 32, 11  # csrc/nr_ssim_loss.h SS_TILE (output tile edge of a block), 2 SS_MAX_R + 1
 NR_ADAM_MAX_TENSORS, NR_ADAM_CHUNK = 24, 4096  # tensors per launch pair, elements of one tensor per block
 NR_ATTR_MAX_CHANNELS = 64
 NR_CHAMFER_X_TO_Y, NR_CHAMFER_Y_TO_X = 1, 2
@@ -150,6 +152,10 @@ SIGNATURES = {
     "nr_pointwise_loss_backward": (c_int, _pointwise + [_P, _P, _P]),
     "nr_iou_loss_forward": (c_int, [_P, c_ll, _P, c_ll, c_float, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "nr_iou_loss_backward": (c_int, [_P, c_ll, _P, c_float, c_int, c_int, _P, _P, _P]),
+    "nr_ssim_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "nr_ssim_loss_forward": (c_int, [_P, c_ll, _P, c_ll, c_int, c_int, c_int, c_int, c_int, _P, c_float, c_float, c_int, _P, _P, _P,
+                                     c_size_t, _P]),
+    "nr_ssim_loss_backward": (c_int, [_P, c_ll, _P, c_ll, _P, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P, _P, _P]),
     "nr_adam_args_size": (c_size_t, []),
     "nr_adam_scratch_bytes": (c_size_t, [c_int]),
     "nr_adam_step": (c_int, [_args(NrAdamArgs), _P]),
@@ -187,7 +193,7 @@ def lib():
         raise RuntimeError("neural_renderer_v2_pytorch_amd: HIP library %s is missing; build it with "
                            "__graft_entry__.build() (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
-    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_adam_*, nr_attributes_*,
+    # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_ssim_loss_*, nr_adam_*, nr_attributes_*,
     # point-loss entry points and the two point / mesh distance directions, nr_point_mesh_* and nr_face_point_*):
     # a library built before them still reports the version this binding expects
     missing = [name for name in EXPORTS if not hasattr(L, name)]

@@ -25,7 +25,7 @@
 // per-pixel shading, XCD tile map), nr_fwd.h (setup + face-index raster), nr_shade.h (image epilogue,
 // halo cache, standalone reference kernels), nr_bwd.h (backward), nr_camera.h (look_at / look +
 // perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian and
-// flatten regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_adam.h
+// flatten regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_ssim_loss.h (SSIM image loss), nr_adam.h
 // (multi-tensor Adam), nr_attributes.h (per-vertex attribute rendering), nr_point_loss.h (chamfer distance,
 // nearest points and surface sampling), nr_point_mesh.h (point-to-surface distance), nr_face_point.h (face-to-scan distance), nr_host.h (workspace layouts, launch helpers, argument checks); this file holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
@@ -61,6 +61,7 @@
 #include "nr_projection.h"
 #include "nr_mesh_loss.h"
 #include "nr_image_loss.h"
+#include "nr_ssim_loss.h"
 #include "nr_adam.h"
 #include "nr_attributes.h"
 #include "nr_point_loss.h"
@@ -1316,6 +1317,103 @@ int nr_iou_loss_backward(const float* targets, long long target_stride, const fl
     nr_launch(vec ? k_iou_bwd<4> : k_iou_bwd<1>, grid, dim3(IL_BLOCK), 0, st, targets, target_stride, sums, grad_loss, eps, N, nchunk,
               grad_images);
     return check_launch("k_iou_bwd");
+}
+
+// ---- SSIM loss (nr_ssim_loss.h) ----
+struct SSGeom {
+    int R = 0, MH = 0, MW = 0;          // window radius, the SSIM map
+    long long N = 0;                    // C H W
+    long long ftiles = 0, btiles = 0;   // tiles per channel: of the map (forward), of the image (backward)
+};
+
+static long long ss_tiles(int h, int w) { return (((long long)h + SS_TILE - 1) / SS_TILE) * (((long long)w + SS_TILE - 1) / SS_TILE); }
+
+// Sizes, window and padding of every SSIM entry point; g->N == 0 or B == 0: nothing to launch.
+static int validate_ssim(int B, int C, int H, int W, int window_size, int padding, SSGeom* g) {
+    if (B < 0 || C < 0 || H < 0 || W < 0) return fail(NR_ERR_ARGS, "bad sizes B=%d C=%d H=%d W=%d", B, C, H, W);
+    if (window_size < 3 || window_size > 2 * SS_MAX_R + 1 || window_size % 2 == 0)
+        return fail(NR_ERR_ARGS, "bad window size %d (odd, 3 to %d)", window_size, 2 * SS_MAX_R + 1);
+    if (padding != NR_SSIM_SAME && padding != NR_SSIM_VALID) return fail(NR_ERR_ARGS, "bad padding %d", padding);
+    g->R = window_size / 2;
+    const long long hw = (long long)H * W;
+    if (hw > INT_MAX || hw * C > INT_MAX) return fail(NR_ERR_ARGS, "too many elements C=%d H=%d W=%d", C, H, W);
+    g->N = hw * C;
+    if (B == 0 || g->N == 0) return NR_OK;
+    g->MH = padding == NR_SSIM_VALID ? H - 2 * g->R : H, g->MW = padding == NR_SSIM_VALID ? W - 2 * g->R : W;
+    if (g->MH < 1 || g->MW < 1)
+        return fail(NR_ERR_ARGS, "a %d x %d image has no 'valid' window of %d", H, W, window_size);
+    g->ftiles = ss_tiles(g->MH, g->MW), g->btiles = ss_tiles(H, W);
+    if ((long long)B * C > INT_MAX || (long long)B * C * g->btiles > INT_MAX)
+        return fail(NR_ERR_ARGS, "too many tiles B=%d C=%d H=%d W=%d", B, C, H, W);
+    return NR_OK;
+}
+
+static int ssim_args(const float* images, long long istride, const float* targets, long long tstride, int B, int C, int H, int W,
+                     const SSGeom& g, const float* window, float c1, float c2, int padding, SSArgs* a) {
+    if (!images || !targets || !window) return fail(NR_ERR_ARGS, "null images, targets or window");
+    if (istride < 0 || tstride < 0) return fail(NR_ERR_ARGS, "negative item stride");
+    if (!(c1 >= 0.f && c1 < INFINITY && c2 >= 0.f && c2 < INFINITY)) return fail(NR_ERR_ARGS, "bad constants c1=%g c2=%g", (double)c1, (double)c2);
+    *a = SSArgs{images, targets, istride, tstride, B, C, H, W, g.MH, g.MW, padding == NR_SSIM_SAME ? g.R : 0, 0, 0, c1, c2, {}};
+    for (int k = 0; k <= 2 * g.R; k++) {
+        if (!(fabsf(window[k]) < INFINITY)) return fail(NR_ERR_ARGS, "window weight %d is not finite", k);
+        a->g[k] = ss_f2{window[k], window[k]};
+    }
+    return NR_OK;
+}
+
+size_t nr_ssim_loss_workspace_bytes(int batch_size, int channels, int height, int width, int window_size, int padding) {
+    SSGeom g;
+    if (validate_ssim(batch_size, channels, height, width, window_size, padding, &g) || batch_size == 0 || g.N == 0) return 0;
+    return align_up((size_t)batch_size * (size_t)channels * (size_t)g.ftiles * 4);
+}
+
+int nr_ssim_loss_forward(const float* images, long long image_stride, const float* targets, long long target_stride,
+                         int batch_size, int channels, int height, int width, int window_size, const float* window, float c1,
+                         float c2, int padding, float* loss, float* saved, void* workspace, size_t workspace_bytes, void* stream) {
+    const int B = batch_size, C = channels, H = height, W = width;
+    SSGeom g;
+    int e = validate_ssim(B, C, H, W, window_size, padding, &g);
+    if (e) return e;
+    if (B == 0) return NR_OK;
+    if (!loss) return fail(NR_ERR_ARGS, "null loss");
+    hipStream_t st = (hipStream_t)stream;
+    if (g.N == 0) {
+        if (!zero_async(loss, (size_t)B * 4, st, &e)) return e;
+        return NR_OK;
+    }
+    SSArgs a;
+    e = ssim_args(images, image_stride, targets, target_stride, B, C, H, W, g, window, c1, c2, padding, &a);
+    if (e) return e;
+    if (!workspace || workspace_bytes < nr_ssim_loss_workspace_bytes(B, C, H, W, window_size, padding))
+        return fail(NR_ERR_WORKSPACE, "ssim loss workspace missing or too small");
+    a.ntx = (g.MW + SS_TILE - 1) / SS_TILE, a.nty = (g.MH + SS_TILE - 1) / SS_TILE;
+    const int nblk = (int)(C * g.ftiles);
+    const dim3 grid((unsigned)(B * nblk));
+    if (saved) ss_launch_fwd<true>(g.R, a, grid, st, (float*)workspace, saved);
+    else ss_launch_fwd<false>(g.R, a, grid, st, (float*)workspace, nullptr);
+    e = check_launch("k_ssim_fwd");
+    if (e) return e;
+    nr_launch(k_ssim_finish, dim3((unsigned)B), dim3(SS_BLOCK), 0, st, (const float*)workspace, nblk,
+              (float)((long long)C * g.MH * g.MW), loss);
+    return check_launch("k_ssim_finish");
+}
+
+int nr_ssim_loss_backward(const float* images, long long image_stride, const float* targets, long long target_stride,
+                          const float* saved, int batch_size, int channels, int height, int width, int window_size,
+                          const float* window, int padding, const float* grad_loss, float* grad_images, void* stream) {
+    const int B = batch_size, C = channels, H = height, W = width;
+    SSGeom g;
+    int e = validate_ssim(B, C, H, W, window_size, padding, &g);
+    if (e) return e;
+    if (B == 0 || g.N == 0) return NR_OK;
+    if (!saved || !grad_loss || !grad_images) return fail(NR_ERR_ARGS, "null saved, grad_loss or grad_images");
+    SSArgs a;
+    e = ssim_args(images, image_stride, targets, target_stride, B, C, H, W, g, window, 0.f, 0.f, padding, &a);
+    if (e) return e;
+    a.ntx = (W + SS_TILE - 1) / SS_TILE, a.nty = (H + SS_TILE - 1) / SS_TILE;
+    const dim3 grid((unsigned)(B * C * g.btiles));
+    ss_launch_bwd(g.R, a, grid, (hipStream_t)stream, saved, grad_loss, (float)((long long)C * g.MH * g.MW), grad_images);
+    return check_launch("k_ssim_bwd");
 }
 
 // ---- optimiser (nr_adam.h) ----

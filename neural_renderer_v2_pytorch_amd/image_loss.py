@@ -1,7 +1,8 @@
 """Per-item image losses for the optimisation loop around the renderer: the weighted squared error, the
-Huber loss and the silhouette IoU loss, each one fused HIP launch pair forward and one launch backward
-(nr_pointwise_loss_* / nr_iou_loss_*, include/nr_raster.h) for float32 GPU images, and a torch
-composition (squared_error_loss_torch / huber_loss_torch / iou_loss_torch) for everything else.
+Huber loss, the silhouette IoU loss and the structural-similarity (SSIM) loss, each one fused HIP launch
+pair forward and one launch backward (nr_pointwise_loss_* / nr_iou_loss_* / nr_ssim_loss_*,
+include/nr_raster.h) for float32 GPU images, and a torch composition (squared_error_loss_torch /
+huber_loss_torch / iou_loss_torch / ssim_loss_torch) for everything else.
 
 Definitions, for images [B, ...] with N elements per item (all the trailing dimensions):
 
@@ -9,6 +10,7 @@ Definitions, for images [B, ...] with N elements per item (all the trailing dime
   Huber:         loss_b = sum_i w_i h(x_i - t_i),  h(d) = d^2 / 2 if |d| < delta else delta (|d| - delta / 2)
                  (torch.nn.functional.huber_loss with reduction='none', weighted and summed per item)
   IoU:           loss_b = 1 - sum_i p_i t_i / (sum_i (p_i + t_i - p_i t_i) + eps)
+  SSIM:          loss_b = 1 - mean of S over the item's map; images [B, C, H, W] or [B, H, W] (ssim_loss)
 
 targets have the images' shape, or are shared by the items: a leading 1, no batch dimension, or a
 batch-expanded view; a shared target is read at stride 0 and never expanded in memory.  weights are None,
@@ -21,6 +23,8 @@ one contiguous run of N floats (rgba[:, 3], rgba[:, :3] and the [:, 0] view of r
 are: the kernels take an item stride); any other layout is made contiguous first.  No host
 synchronisation, so a step can be captured in a HIP graph, and no float atomics: losses and gradients
 are bitwise identical from run to run."""
+import functools
+
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -110,6 +114,68 @@ def iou_loss_torch(silhouettes, targets, eps=1e-6, average=False):
     inter = pt.sum(dims)
     union = (silhouettes + targets - pt).sum(dims)
     return _finish(1 - inter / (union + eps), average)
+
+
+# ---- SSIM: definition and composition ----
+_SSIM_PADDINGS = ("same", "valid")
+
+
+def _ssim_window(window_size, sigma):
+    """The 1-D Gaussian window exp(-k^2 / 2 sigma^2), k = -R .. R, normalised to sum 1: a float64 tensor."""
+    R = window_size // 2
+    k = torch.arange(-R, R + 1, dtype=torch.float64)
+    g = torch.exp(-(k * k) / (2.0 * float(sigma) ** 2))
+    return g / g.sum()
+
+
+@functools.lru_cache(maxsize=64)
+def _ssim_window_on(window_size, sigma, dtype, device):
+    """The window in the composition's dtype on its device, kept: a step that was run once makes no host-to-device
+    copy again, so it can be captured in a graph."""
+    return _ssim_window(window_size, sigma).to(dtype=dtype, device=device)
+
+
+def _ssim_check(images, targets, window_size, sigma, data_range, padding):
+    """The argument errors of both paths; returns (images, targets) as 4-D [B, C, H, W] / [B or 1, C, H, W] views."""
+    if not torch.is_tensor(images) or images.ndim not in (3, 4):
+        raise ValueError("images must be a [B, C, H, W] or [B, H, W] tensor")
+    _check_targets(images, targets)
+    if not isinstance(window_size, int) or window_size < 1 or window_size % 2 == 0:
+        raise ValueError("window_size must be a positive odd integer, not %r" % (window_size,))
+    if padding not in _SSIM_PADDINGS:
+        raise ValueError("padding must be 'same' or 'valid', not %r" % (padding,))
+    if not (0 < sigma < float("inf")) or not (0 < data_range < float("inf")):
+        raise ValueError("sigma and data_range must be positive and finite")
+    if padding == "valid" and images.numel() and (images.shape[-2] < window_size or images.shape[-1] < window_size):
+        raise ValueError("padding='valid' needs images of at least %d x %d pixels, not %d x %d"
+                         % (window_size, window_size, images.shape[-2], images.shape[-1]))
+    t = targets if targets.ndim == images.ndim else targets[None]
+    if images.ndim == 3:
+        images, t = images[:, None], t[:, None]
+    return images, t
+
+
+def ssim_loss_torch(images, targets, window_size=11, sigma=1.5, data_range=1.0, padding="same", average=False):
+    """The SSIM loss as torch ops (two grouped 1-D convolutions per filtered quantity); any device and dtype,
+    gradients to both operands.  The definition: ssim_loss."""
+    x, t = _ssim_check(images, targets, window_size, sigma, data_range, padding)
+    dtype = torch.result_type(x, t)  # mixed operands promote, as in the pointwise compositions
+    x, t = x.to(dtype), t.to(dtype)
+    C, R = x.shape[1], window_size // 2
+    g = _ssim_window_on(window_size, float(sigma), x.dtype, x.device)
+    row, col = g.reshape(1, 1, 1, -1).repeat(C, 1, 1, 1), g.reshape(1, 1, -1, 1).repeat(C, 1, 1, 1)
+    pad = R if padding == "same" else 0
+    conv2d = torch.nn.functional.conv2d
+
+    def G(a):
+        return conv2d(conv2d(a, row, padding=(0, pad), groups=C), col, padding=(pad, 0), groups=C)
+
+    c1, c2 = (0.01 * data_range) ** 2, (0.03 * data_range) ** 2
+    mu1, mu2 = G(x), G(t)
+    mu11, mu22, mu12 = mu1 * mu1, mu2 * mu2, mu1 * mu2
+    s11, s22, s12 = G(x * x) - mu11, G(t * t) - mu22, G(x * t) - mu12
+    S = ((2 * mu12 + c1) * (2 * s12 + c2)) / ((mu11 + mu22 + c1) * (s11 + s22 + c2))
+    return _finish(1 - S.mean((1, 2, 3)), average)
 
 
 # ---- the fused path ----
@@ -239,6 +305,51 @@ class IoULossFunction(torch.autograd.Function):
         return grad, None, None, None, None
 
 
+class SSIMLossFunction(torch.autograd.Function):
+    """images [B, C, H, W] float32 on the GPU, every item contiguous -> loss [B].  When the images take a
+    gradient the forward keeps the three maps [3, B, C, H', W'] of include/nr_raster.h; the backward
+    filters them and reads images and targets, which are saved by reference."""
+
+    @staticmethod
+    def forward(ctx, images, istride, targets, tstride, window, c1, c2, padding):
+        B, C, H, W = images.shape
+        dev = images.device
+        L = _lib.lib()
+        K = len(window)
+        R = K // 2
+        win = (_lib.c_float * K)(*window)
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        ws = torch.empty(L.nr_ssim_loss_workspace_bytes(B, C, H, W, K, padding), dtype=torch.uint8, device=dev)
+        saved = None
+        if ctx.needs_input_grad[0]:
+            mh, mw = (H - 2 * R, W - 2 * R) if padding == _lib.NR_SSIM_VALID else (H, W)
+            saved = torch.empty((3, B, C, max(mh, 0), max(mw, 0)), dtype=torch.float32, device=dev)
+        with _lib.on_device(dev):
+            _lib.check(L.nr_ssim_loss_forward(_lib.ptr(images), istride, _lib.ptr(targets), tstride, B, C, H, W, K, win, c1, c2,
+                                              padding, _lib.ptr(loss), _lib.ptr(saved), _lib.ptr(ws), ws.numel(),
+                                              _lib.stream_of(images)), "nr_ssim_loss_forward")
+        if saved is not None:
+            ctx.save_for_backward(images, targets, saved)
+            ctx.args = (istride, tstride, win, padding)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        images, targets, saved = ctx.saved_tensors
+        istride, tstride, win, padding = ctx.args
+        B, C, H, W = images.shape
+        g = grad_loss.to(torch.float32).contiguous()
+        grad = torch.empty(images.shape, dtype=torch.float32, device=images.device)
+        with _lib.on_device(images.device):
+            _lib.check(_lib.lib().nr_ssim_loss_backward(_lib.ptr(images), istride, _lib.ptr(targets), tstride, _lib.ptr(saved),
+                                                        B, C, H, W, len(win), win, padding, _lib.ptr(g), _lib.ptr(grad),
+                                                        _lib.stream_of(images)), "nr_ssim_loss_backward")
+        return (grad,) + (None,) * 7
+
+
 def _pointwise(images, targets, weights, kind, delta):
     _check_targets(images, targets)
     x, istride = _image_items(images)
@@ -284,6 +395,35 @@ def iou_loss(silhouettes, targets, eps=1e-6, average=False):
     return _finish(IoULossFunction.apply(x, istride, t, tstride, float(eps)), average)
 
 
+def ssim_loss(images, targets, window_size=11, sigma=1.5, data_range=1.0, padding="same", average=False):
+    """1 - the mean structural similarity (Wang et al. 2004) per item: [B] for images [B, C, H, W] or
+    [B, H, W] (C = 1), or with average=True the 0-dim mean over the items.  Targets as the other losses take.
+
+    g is the window exp(-k^2 / 2 sigma^2), k = -R .. R, R = window_size // 2, computed in float64,
+    normalised to sum 1 and cast to the images' dtype; G = g (x) g filters each channel.  With
+    C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2, mu1 = G*x, mu2 = G*t, s11 = G*x^2 - mu1^2,
+    s22 = G*t^2 - mu2^2, s12 = G*(x t) - mu1 mu2 (no variance clamp):
+
+      S = (2 mu1 mu2 + C1) (2 s12 + C2) / ((mu1^2 + mu2^2 + C1) (s11 + s22 + C2))
+      loss_b = 1 - mean of S over the item's map (all channels and map pixels)
+
+    padding='same' pads with R zeros, the map is H x W (the Gaussian-splatting loss); padding='valid' does
+    not pad, the map is (H - 2R) x (W - 2R) (pytorch-msssim, skimage) and H, W >= window_size.
+
+    The fused path (module docstring) also needs window_size in 3, 5, 7, 9, 11; anything else runs
+    ssim_loss_torch.  An even window, an unknown padding, a non-positive sigma or data_range and targets
+    that do not fit raise ValueError on both paths."""
+    x, t = _ssim_check(images, targets, window_size, sigma, data_range, padding)
+    if not _fusable(images, targets) or not 3 <= window_size <= _lib.NR_SSIM_MAX_WINDOW:
+        return ssim_loss_torch(images, targets, window_size, sigma, data_range, padding, average)
+    window = _ssim_window(window_size, sigma).to(torch.float32).tolist()
+    x, istride = _image_items(x)
+    t, tstride = _items(t, _shared(targets, images))
+    loss = SSIMLossFunction.apply(x, istride, t, tstride, tuple(window), (0.01 * data_range) ** 2, (0.03 * data_range) ** 2,
+                                  _lib.NR_SSIM_VALID if padding == "valid" else _lib.NR_SSIM_SAME)
+    return _finish(loss, average)
+
+
 class _TargetLoss(torch.nn.Module):
     def __init__(self, targets, weights, average):
         super().__init__()
@@ -322,3 +462,14 @@ class IoULoss(_TargetLoss):
 
     def forward(self, silhouettes):
         return iou_loss(silhouettes, self.targets, self.eps, self.average)
+
+
+class SSIMLoss(_TargetLoss):
+    """ssim_loss with the targets held as a buffer of the module."""
+
+    def __init__(self, targets, window_size=11, sigma=1.5, data_range=1.0, padding="same", average=False):
+        super().__init__(targets, None, average)
+        self.window_size, self.sigma, self.data_range, self.padding = window_size, sigma, data_range, padding
+
+    def forward(self, images):
+        return ssim_loss(images, self.targets, self.window_size, self.sigma, self.data_range, self.padding, self.average)
