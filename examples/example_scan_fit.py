@@ -14,10 +14,12 @@ the loss carries sampling noise of the order of the sample spacing.  Here
                  triangle to its nearest scan point: no samples are drawn, and the whole scan loss is exact;
 
 plus a small nr.laplacian_loss that keeps the surface smooth, stepped by nr.Adam: every operation of the
-step is a fused HIP kernel.
+step is a fused HIP kernel.  --laplacian cot takes nr.cot_laplacian_loss instead (it leaves an irregular
+triangulation of a flat patch alone), and --edge-weight W adds W * nr.edge_length_loss towards the
+icosphere's mean initial edge length, which keeps the triangles from stretching and collapsing.
 
     python examples/example_scan_fit.py [--iters 300] [--samples 5000] [--level 3] [--mesh-to-scan sampled|exact]
-                                        [--out fitted.obj]
+                                        [--laplacian uniform|cot] [--edge-weight 0] [--out fitted.obj]
 
 The target mesh defaults to tests/data/teapot.obj.
 """
@@ -35,7 +37,8 @@ DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'tests', '
 
 
 class ScanFit(torch.nn.Module):
-    def __init__(self, obj_file, level, samples, smoothness, device, seed=0, mesh_to_scan='sampled'):
+    def __init__(self, obj_file, level, samples, smoothness, device, seed=0, mesh_to_scan='sampled', laplacian='uniform',
+                 edge_weight=0.):
         super().__init__()
         self.generator = torch.Generator(device=device).manual_seed(seed)
         vertices, faces = nr.load_obj(obj_file)
@@ -51,14 +54,24 @@ class ScanFit(torch.nn.Module):
         self.vertices = torch.nn.Parameter(torch.as_tensor(sphere).float().to(device))
         self.topology = nr.mesh_topology(self.faces, sphere.shape[0])
         self.samples, self.smoothness = samples, smoothness
+        self.laplacian = nr.cot_laplacian_loss if laplacian == 'cot' else nr.laplacian_loss
+        self.edge_weight = edge_weight
+        corners = torch.as_tensor(sphere)[torch.as_tensor(sphere_faces).long()]  # [F, 3, 3]
+        self.edge_length = float((corners - corners.roll(1, 1)).norm(dim=-1).mean())  # a closed mesh: every edge twice
+
+    def regularizer(self):
+        """The weighted regularizers: the Laplacian loss, and the edge-length loss if asked for."""
+        total = self.smoothness * self.laplacian(self.vertices, self.topology)
+        if self.edge_weight:
+            total = total + self.edge_weight * nr.edge_length_loss(self.vertices, self.topology, self.edge_length)
+        return total
 
     def forward(self):
         if self.exact:
             return (self.scan_to_mesh(self.vertices, self.faces), self.mesh_to_scan(self.vertices, self.faces),
-                    nr.laplacian_loss(self.vertices, self.topology))
+                    self.regularizer())
         points = nr.sample_points(self.vertices, self.faces, self.samples, generator=self.generator)
-        return (self.scan_to_mesh(self.vertices, self.faces), self.mesh_to_scan(points),
-                nr.laplacian_loss(self.vertices, self.topology))
+        return self.scan_to_mesh(self.vertices, self.faces), self.mesh_to_scan(points), self.regularizer()
 
 
 def parser():
@@ -71,6 +84,9 @@ def parser():
     ap.add_argument('--gpu', type=int, default=0)
     ap.add_argument('--mesh-to-scan', choices=('sampled', 'exact'), default='sampled',
                     help="the mesh -> scan term: fresh surface samples and a one-sided chamfer term, or nr.MeshPointLoss")
+    ap.add_argument('--laplacian', choices=('uniform', 'cot'), default='uniform',
+                    help='nr.laplacian_loss (every neighbour weighs the same) or nr.cot_laplacian_loss')
+    ap.add_argument('--edge-weight', type=float, default=0., help='weight of nr.edge_length_loss (0: not computed)')
     ap.add_argument('--out', default=None, help='write the fitted mesh as an .obj file')
     return ap
 
@@ -78,13 +94,13 @@ def parser():
 def main():
     args = parser().parse_args()
     model = ScanFit(args.obj, args.level, args.samples, args.smoothness, torch.device('cuda', args.gpu),
-                    mesh_to_scan=args.mesh_to_scan)
+                    mesh_to_scan=args.mesh_to_scan, laplacian=args.laplacian, edge_weight=args.edge_weight)
     opt = nr.Adam(model.parameters(), lr=0.01)
     history = []
     for _ in range(args.iters):
         opt.zero_grad()
-        to_mesh, to_scan, laplacian = model()
-        (to_mesh + to_scan + args.smoothness * laplacian).backward()
+        to_mesh, to_scan, regularizer = model()
+        (to_mesh + to_scan + regularizer).backward()
         opt.step()
         history.append((float(to_mesh.detach()), float(to_scan.detach())))
     print('scan -> mesh: first %.5f, last %.5f; mesh -> scan: first %.5f, last %.5f after %d steps'

@@ -345,6 +345,55 @@ NR_API int nr_flatten_backward(const float* records, const int32_t* edge_offsets
                                const float* grad_loss, int batch_size, int num_vertices, int num_edges,
                                float* grad_vertices, void* stream);
 
+/* Two more regularizers on the same neighbour CSR and the same conventions.  Faces with a repeated vertex
+ * index are ignored by both (the CSR holds no edge of theirs).
+ *
+ * Edge length: E = the distinct undirected edges {i, j} of the faces -- the pairs j in N(i), j > i;
+ * boundary and non-manifold edges count once each.  With len_ij = |v_i - v_j| and L = target_length >= 0:
+ *   loss_b = sum_{ {i,j} in E } (len_ij - L)^2
+ *   grad v_i = 2 g_b sum_{j in N(i)} (len_ij - L) / len_ij * (v_i - v_j)
+ * An edge with len_ij == 0 contributes L^2 to the loss and nothing to the gradient.  The backward
+ * recomputes from the vertices; the workspace is nr_mesh_loss_workspace_bytes(B, V).
+ *
+ * Cotangent Laplacian: for corner k of face f (faces [F, 3] int32), a and b the edge vectors leaving it,
+ *   c_{f,k} = 0.5 (a . b) / sqrt(|a x b|^2 + eps)
+ * Corner (f, k) is opposite the edge of the face's two other corners.  Every entry e = (i, j) of the
+ * neighbour CSR lists its opposite corners 3 f + k, ascending, in nbr_corners [nbr_corner_offsets[e] ..
+ * nbr_corner_offsets[e + 1]) (nbr_corner_offsets [nnz + 1], nnz = num_neighbours = nbr_offsets[V]); the
+ * entries (i, j) and (j, i) hold the same list.  A boundary edge has one corner, a manifold edge two.
+ *   w_ij = max(0, sum of c_{f,k} over the list of (i, j), in list order)      (so w_ij == w_ji bit for bit)
+ *   W_i  = sum_{j in N(i)} w_ij  (CSR order);   ok_i = W_i > NR_COT_MIN_WEIGHT
+ *   delta_i = ok_i ? v_i - (sum_j w_ij v_j) / W_i : 0;   loss_b = sum_i |delta_i|^2
+ * The clamp keeps the weighted mean a convex combination where both opposite angles are obtuse.  The
+ * weights are constants of the backward (no gradient flows through them):
+ *   grad v_k = 2 g_b (delta_k - sum_{i in N(k)} w_ki Winv_i delta_i),   Winv_i = ok_i ? 1 / W_i : 0
+ * Limits: those above with E2 = 0, and B * ceil(F / 256) <= INT_MAX, 3 F < 2^31.  The corner lists are
+ * trusted: every corner below 3 F and of a face without a repeated index. */
+#define NR_COT_MIN_WEIGHT 1e-6f
+/* loss [B], fully written (0 when V == 0). */
+NR_API int nr_edge_length_forward(const float* vertices, const int32_t* nbr_offsets, const int32_t* nbr_index,
+                                  int batch_size, int num_vertices, float target_length, float* loss,
+                                  void* workspace, size_t workspace_bytes, void* stream);
+/* grad_loss [B] -> grad_vertices [B, V, 3], fully written, from the forward's vertices. */
+NR_API int nr_edge_length_backward(const float* vertices, const int32_t* nbr_offsets, const int32_t* nbr_index,
+                                   const float* grad_loss, int batch_size, int num_vertices, float target_length,
+                                   float* grad_vertices, void* stream);
+/* Scratch bytes of nr_cot_laplacian_forward: the per-block partial sums [B][ceil(V / 256)], then the
+ * half-cotangents [B][3 F]; no zero fill needed. */
+NR_API size_t nr_cot_laplacian_workspace_bytes(int batch_size, int num_vertices, int num_faces);
+/* loss [B], fully written (0 when V == 0).  What the backward reads, each fully written or NULL:
+ * delta [B, V, 3], w [B, nnz] (the weight of every CSR entry) and winv [B, V]. */
+NR_API int nr_cot_laplacian_forward(const float* vertices, const int32_t* faces, const int32_t* nbr_offsets,
+                                    const int32_t* nbr_index, const int32_t* nbr_corner_offsets,
+                                    const int32_t* nbr_corners, int batch_size, int num_vertices, int num_faces,
+                                    int num_neighbours, float eps, float* delta, float* w, float* winv, float* loss,
+                                    void* workspace, size_t workspace_bytes, void* stream);
+/* grad_loss [B] -> grad_vertices [B, V, 3], fully written, from the forward's delta, w and winv. */
+NR_API int nr_cot_laplacian_backward(const float* delta, const float* w, const float* winv,
+                                     const int32_t* nbr_offsets, const int32_t* nbr_index, const float* grad_loss,
+                                     int batch_size, int num_vertices, int num_neighbours, float* grad_vertices,
+                                     void* stream);
+
 /* Image losses (image_loss.py): per-item reductions of images [B, N] float32, item b being the N
  * contiguous floats at images + b * image_stride (strides in elements, >= 0).  targets: item b at
  * targets + b * target_stride, 0 = one target shared by every item.  No float atomics: losses and

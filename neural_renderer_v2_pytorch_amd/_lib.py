@@ -64,6 +64,7 @@ NR_POINT_MESH_TILE, NR_POINT_MESH_QBLOCK = 256, 1024  # csrc/nr_point_mesh.h PM_
 NR_POINT_MESH_SPLIT_BLOCKS = 4096  # PM_SPLIT_BLOCKS: the faces are split over further blocks while a launch has fewer
 NR_FACE_POINT_TILE, NR_FACE_POINT_FBLOCK = 64, 256  # csrc/nr_face_point.h FP_TILE (points in LDS), FP_FBLOCK (faces per block)
 NR_FACE_POINT_SPLIT_BLOCKS = 4096  # FP_SPLIT_BLOCKS: the points are split over further blocks while a launch has fewer
+NR_COT_MIN_WEIGHT = 1e-6  # include/nr_raster.h: a vertex whose cotangent weights sum to no more has delta = 0
 
 
 class NrCameraArgs(ctypes.Structure):  # include/nr_raster.h
@@ -147,6 +148,12 @@ SIGNATURES = {
     "nr_laplacian_backward": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P]),
     "nr_flatten_forward": (c_int, [_P, _P, c_int, c_int, c_int, c_float, _P, _P, _P, c_size_t, _P]),
     "nr_flatten_backward": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
+    "nr_edge_length_forward": (c_int, [_P, _P, _P, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
+    "nr_edge_length_backward": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, _P, _P]),
+    "nr_cot_laplacian_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "nr_cot_laplacian_forward": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, c_size_t,
+                                         _P]),
+    "nr_cot_laplacian_backward": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
     "nr_image_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
     "nr_pointwise_loss_forward": (c_int, _pointwise + [_P, _P, c_size_t, _P]),
     "nr_pointwise_loss_backward": (c_int, _pointwise + [_P, _P, _P]),

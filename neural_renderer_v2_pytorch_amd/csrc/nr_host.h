@@ -120,6 +120,16 @@ HaloLayout halo_layout(int B, int S, int C) {
     return {flags, flags + (((size_t)B * make_geom(0, S).nbins + 3) & ~size_t(3))};
 }
 
+// cotangent Laplacian forward (nr_mesh_loss.h): the per-block partial sums [B][blocks of ML_BLOCK vertices],
+// then the half-cotangents [B][3 F] the face pass leaves for the vertex pass
+struct CotLayout {
+    size_t partial, cot, total;
+};
+CotLayout cot_layout(int B, int V, int F) {
+    Cutter c;
+    return {c.take((size_t)B * (((size_t)V + ML_BLOCK - 1) / ML_BLOCK) * 4), c.take((size_t)B * F * 3 * 4), c.off};
+}
+
 // How a nearest-neighbour launch (a chamfer direction: PL_*, a PairDir: PM_* or FP_*) is cut: query blocks per
 // item, and target ranges per query block (more than one -- the split path -- while the launch has fewer
 // than split_blocks blocks and every range still holds at least a full tile of targets: few queries against

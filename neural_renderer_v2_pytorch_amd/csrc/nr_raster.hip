@@ -24,8 +24,8 @@
 // Source layout (one translation unit): nr_common.h (errors, profiling, geometry, exact division,
 // per-pixel shading, XCD tile map), nr_fwd.h (setup + face-index raster), nr_shade.h (image epilogue,
 // halo cache, standalone reference kernels), nr_bwd.h (backward), nr_camera.h (look_at / look +
-// perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian and
-// flatten regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_ssim_loss.h (SSIM image loss), nr_adam.h
+// perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian, cotangent
+// Laplacian, flatten and edge-length regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_ssim_loss.h (SSIM image loss), nr_adam.h
 // (multi-tensor Adam), nr_attributes.h (per-vertex attribute rendering), nr_point_loss.h (chamfer distance,
 // nearest points and surface sampling), nr_point_mesh.h (point-to-surface distance), nr_face_point.h (face-to-scan distance), nr_host.h (workspace layouts, launch helpers, argument checks); this file holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
@@ -897,6 +897,115 @@ int nr_flatten_backward(const float* records, const int32_t* edge_offsets, const
     nr_launch(k_flat_bwd_gather, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, (hipStream_t)stream, records, edge_offsets,
               edge_slots, grad_loss, V, E2, nblk, grad_vertices);
     return check_launch("k_flat_bwd_gather");
+}
+
+int nr_edge_length_forward(const float* vertices, const int32_t* nbr_offsets, const int32_t* nbr_index, int batch_size,
+                           int num_vertices, float target_length, float* loss, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+    const int B = batch_size, V = num_vertices;
+    int e = validate_mesh_loss(B, V, 0);
+    if (e) return e;
+    if (B == 0) return NR_OK;
+    if (!loss) return fail(NR_ERR_ARGS, "null loss");
+    if (!(target_length >= 0.f) || !(target_length < INFINITY))
+        return fail(NR_ERR_ARGS, "bad target_length %g", (double)target_length);
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = (int)ml_blocks(V);
+    if (V > 0) {
+        if (!vertices || !nbr_offsets) return fail(NR_ERR_ARGS, "null vertices or nbr_offsets");
+        if (!workspace || workspace_bytes < nr_mesh_loss_workspace_bytes(B, V))
+            return fail(NR_ERR_WORKSPACE, "mesh loss workspace missing or too small");
+        nr_launch(k_edge_fwd, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, st, vertices, nbr_offsets, nbr_index, V, nblk,
+                  target_length, (float*)workspace);
+        e = check_launch("k_edge_fwd");
+        if (e) return e;
+    }
+    nr_launch(k_mesh_loss_sum, dim3((unsigned)B), dim3(ML_BLOCK), 0, st, (const float*)workspace, nblk, loss);
+    return check_launch("k_mesh_loss_sum");
+}
+
+int nr_edge_length_backward(const float* vertices, const int32_t* nbr_offsets, const int32_t* nbr_index, const float* grad_loss,
+                            int batch_size, int num_vertices, float target_length, float* grad_vertices, void* stream) {
+    const int B = batch_size, V = num_vertices;
+    int e = validate_mesh_loss(B, V, 0);
+    if (e) return e;
+    if (!(target_length >= 0.f) || !(target_length < INFINITY))
+        return fail(NR_ERR_ARGS, "bad target_length %g", (double)target_length);
+    if (B == 0 || V == 0) return NR_OK;
+    if (!vertices || !nbr_offsets || !grad_loss || !grad_vertices) return fail(NR_ERR_ARGS, "null pointer");
+    const int nblk = (int)ml_blocks(V);
+    nr_launch(k_edge_bwd, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, (hipStream_t)stream, vertices, nbr_offsets, nbr_index,
+              grad_loss, V, nblk, target_length, grad_vertices);
+    return check_launch("k_edge_bwd");
+}
+
+// num_neighbours: the entries of the neighbour CSR, below 2^31 as an int
+static int validate_cot_laplacian(int B, int V, int F, int nnz) {
+    if (F < 0 || nnz < 0) return fail(NR_ERR_ARGS, "bad sizes F=%d num_neighbours=%d", F, nnz);
+    int e = validate_mesh_loss(B, V, 0);
+    if (e) return e;
+    if (F > INT_MAX / 3) return fail(NR_ERR_ARGS, "too many faces F=%d (3 * F must stay below 2^31)", F);
+    if ((long long)B * ml_blocks(F) > INT_MAX) return fail(NR_ERR_ARGS, "too many faces B=%d F=%d", B, F);
+    return NR_OK;
+}
+
+size_t nr_cot_laplacian_workspace_bytes(int batch_size, int num_vertices, int num_faces) {
+    if (batch_size <= 0 || num_vertices <= 0 || num_faces < 0 || num_faces > INT_MAX / 3) return 0;
+    return cot_layout(batch_size, num_vertices, num_faces).total;
+}
+
+int nr_cot_laplacian_forward(const float* vertices, const int32_t* faces, const int32_t* nbr_offsets, const int32_t* nbr_index,
+                             const int32_t* nbr_corner_offsets, const int32_t* nbr_corners, int batch_size, int num_vertices,
+                             int num_faces, int num_neighbours, float eps, float* delta, float* w, float* winv, float* loss,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    const int B = batch_size, V = num_vertices, F = num_faces, nnz = num_neighbours;
+    int e = validate_cot_laplacian(B, V, F, nnz);
+    if (e) return e;
+    if (B == 0) return NR_OK;
+    if (!loss) return fail(NR_ERR_ARGS, "null loss");
+    if (!(eps >= 0.f) || !(eps < INFINITY)) return fail(NR_ERR_ARGS, "bad eps %g", (double)eps);
+    if (V == 0 && (F > 0 || nnz > 0)) return fail(NR_ERR_ARGS, "faces or neighbours without vertices");
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = (int)ml_blocks(V);
+    float* partial = nullptr;
+    if (V > 0) {
+        if (!vertices || !nbr_offsets) return fail(NR_ERR_ARGS, "null vertices or nbr_offsets");
+        if (nnz > 0 && (!nbr_index || !nbr_corner_offsets || !nbr_corners || !faces || F == 0))
+            return fail(NR_ERR_ARGS, "neighbours without nbr_index, corner lists or faces");
+        if (F > 0 && !faces) return fail(NR_ERR_ARGS, "null faces");
+        const CotLayout lay = cot_layout(B, V, F);
+        if (!workspace || workspace_bytes < lay.total)
+            return fail(NR_ERR_WORKSPACE, "cotangent Laplacian workspace missing or too small");
+        partial = (float*)((char*)workspace + lay.partial);
+        float* cot = (float*)((char*)workspace + lay.cot);
+        if (F > 0) {
+            const int fblk = (int)ml_blocks(F);
+            nr_launch(k_cot_face, dim3((unsigned)(B * fblk)), dim3(ML_BLOCK), 0, st, vertices, faces, V, F, fblk, eps, cot);
+            e = check_launch("k_cot_face");
+            if (e) return e;
+        }
+        nr_launch(k_cotlap_fwd, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, st, vertices, nbr_offsets, nbr_index,
+                  nbr_corner_offsets, nbr_corners, (const float*)cot, V, F, nnz, nblk, w, winv, delta, partial);
+        e = check_launch("k_cotlap_fwd");
+        if (e) return e;
+    }
+    nr_launch(k_mesh_loss_sum, dim3((unsigned)B), dim3(ML_BLOCK), 0, st, (const float*)partial, nblk, loss);
+    return check_launch("k_mesh_loss_sum");
+}
+
+int nr_cot_laplacian_backward(const float* delta, const float* w, const float* winv, const int32_t* nbr_offsets,
+                              const int32_t* nbr_index, const float* grad_loss, int batch_size, int num_vertices,
+                              int num_neighbours, float* grad_vertices, void* stream) {
+    const int B = batch_size, V = num_vertices, nnz = num_neighbours;
+    int e = validate_cot_laplacian(B, V, 0, nnz);
+    if (e) return e;
+    if (B == 0 || V == 0) return NR_OK;
+    if (!delta || !winv || !nbr_offsets || !grad_loss || !grad_vertices) return fail(NR_ERR_ARGS, "null pointer");
+    if (nnz > 0 && (!w || !nbr_index)) return fail(NR_ERR_ARGS, "null w or nbr_index");
+    const int nblk = (int)ml_blocks(V);
+    nr_launch(k_cotlap_bwd, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, (hipStream_t)stream, delta, w, winv, nbr_offsets,
+              nbr_index, grad_loss, V, nnz, nblk, grad_vertices);
+    return check_launch("k_cotlap_bwd");
 }
 
 // ---- point losses (nr_point_loss.h) ----

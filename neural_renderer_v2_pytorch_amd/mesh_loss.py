@@ -1,7 +1,8 @@
 """Mesh regularizers for the optimisation loop around the renderer: the uniform Laplacian smoothness
-loss and the dihedral 'flatten' loss, each one fused HIP launch pair forward and one launch backward
-(nr_laplacian_* / nr_flatten_*, include/nr_raster.h) for float32 GPU vertices, and a torch composition
-(laplacian_loss_torch / flatten_loss_torch) for every other device and dtype.
+loss, the dihedral 'flatten' loss, the edge-length loss and the cotangent-weighted Laplacian loss, each
+a few fused HIP launches forward and one launch backward (nr_laplacian_* / nr_flatten_* /
+nr_edge_length_* / nr_cot_laplacian_*, include/nr_raster.h) for float32 GPU vertices, and a torch
+composition (*_loss_torch) for every other device and dtype.
 
 Definitions, for vertices [B, V, 3] and faces [F, 3] shared by every item.  Faces with a repeated
 vertex index are ignored by both losses; duplicate faces count separately.
@@ -14,6 +15,15 @@ vertex index are ignored by both losses; duplicate faces count separately.
              lower- / higher-numbered face:  a = v1 - v0, b_k = v_{k+1} - v0,
              c_k = b_k - a (a . b_k) / (|a|^2 + eps),
              cos = (c_1 . c_2) / (sqrt(|c_1|^2 + eps) sqrt(|c_2|^2 + eps)), loss_b = sum_edges (cos + 1)^2.
+  Edge length: over every distinct undirected edge {i, j} of the faces (boundary and non-manifold edges
+             once each; MeshTopology.num_all_edges of them), loss_b = sum (|v_i - v_j| - target_length)^2.
+             An edge of length 0 adds target_length^2 and takes no gradient.
+  Cotangent Laplacian: c_{f,k} = 0.5 (a . b) / sqrt(|a x b|^2 + eps) at corner k of face f, a and b the
+             edge vectors leaving it; w_ij = max(0, sum of c over the corners opposite edge {i, j});
+             W_i = sum_{j in N(i)} w_ij; delta_i = v_i - (sum_j w_ij v_j) / W_i where W_i > COT_MIN_WEIGHT,
+             else 0; loss_b = sum_i |delta_i|^2.  The clamp keeps the weighted mean a convex combination
+             where both angles opposite an edge are obtuse.  The weights are constants of the backward:
+             no gradient flows through them, in the fused path and in the composition alike.
 
 The topology (mesh_topology) is built on the host once per faces tensor and cached, so steady-state
 calls issue no host synchronisation and a step can be captured in a HIP graph.  The fused kernels use
@@ -74,6 +84,50 @@ def flatten_loss_torch(vertices, faces, eps=1e-6, average=False):
     c2 = b2 - a * ((a * b2).sum(-1, keepdim=True) / la)
     cos = (c1 * c2).sum(-1) / (torch.sqrt((c1 * c1).sum(-1) + eps) * torch.sqrt((c2 * c2).sum(-1) + eps))
     return _finish(((cos + 1) ** 2).sum(1), single, average)
+
+
+COT_MIN_WEIGHT = _lib.NR_COT_MIN_WEIGHT  # a vertex whose weights sum to no more has delta = 0
+
+
+def edge_length_loss_torch(vertices, faces, target_length=0.0, average=False):
+    """The edge-length loss as torch ops (index_select over the neighbour entries j > i); any device and
+    floating dtype.  A `where` keeps the square root's gradient away from edges of length 0."""
+    v, single, topo = _prepare(vertices, faces)
+    i, j = topo.edge_index()
+    d = v.index_select(1, i) - v.index_select(1, j)
+    d2 = (d * d).sum(-1)
+    zero = d2 == 0
+    length = torch.where(zero, torch.zeros_like(d2), torch.sqrt(torch.where(zero, torch.ones_like(d2), d2)))
+    return _finish(((length - target_length) ** 2).sum(1), single, average)
+
+
+def cot_weights_torch(v, topo, eps=1e-12):
+    """The clamped cotangent weight of every neighbour entry, [B, nnz], of vertices [B, V, 3]: computed
+    without gradient (the weights are constants of the loss's backward)."""
+    with torch.no_grad():
+        f, entry, corners = topo.cot_composition_index()
+        p = [v.index_select(1, f[:, k]) for k in range(3)]
+        c = []
+        for k in range(3):
+            a, b = p[(k + 1) % 3] - p[k], p[(k + 2) % 3] - p[k]
+            n = torch.linalg.cross(a, b)
+            c.append(0.5 * (a * b).sum(-1) / torch.sqrt((n * n).sum(-1) + eps))
+        c = torch.stack(c, -1).reshape(v.shape[0], -1)  # [B, 3 F]; corners of ignored faces are never selected
+        w = torch.zeros((v.shape[0], topo.nbr_index.numel()), dtype=v.dtype, device=v.device)
+        return w.index_add_(1, entry, c.index_select(1, corners)).clamp_(min=0)
+
+
+def cot_laplacian_loss_torch(vertices, faces, eps=1e-12, average=False):
+    """The cotangent Laplacian loss as torch ops; any device and floating dtype.  The weights carry no
+    gradient."""
+    v, single, topo = _prepare(vertices, faces)
+    rows, cols = topo.composition_index()[:2]
+    w = cot_weights_torch(v.detach(), topo, eps)
+    W = torch.zeros(v.shape[:2], dtype=v.dtype, device=v.device).index_add_(1, rows, w)
+    ok = W > COT_MIN_WEIGHT
+    total = torch.zeros_like(v).index_add_(1, rows, w[:, :, None] * v.index_select(1, cols))
+    delta = (v - total / torch.where(ok, W, torch.ones_like(W))[:, :, None]) * ok.to(v.dtype)[:, :, None]
+    return _finish((delta * delta).sum((1, 2)), single, average)
 
 
 # ---- the fused path ----
@@ -158,6 +212,87 @@ class FlattenFunction(torch.autograd.Function):
         return gv, None, None
 
 
+class EdgeLengthFunction(torch.autograd.Function):
+    """vertices [B, V, 3] float32 contiguous on the GPU -> loss [B]; the backward recomputes from the saved
+    vertices."""
+
+    @staticmethod
+    def forward(ctx, vertices, topo, target_length):
+        B, V = vertices.shape[0], vertices.shape[1]
+        dev = vertices.device
+        L = _lib.lib()
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        ws = _workspace(L, B, V, dev)
+        with _lib.on_device(dev):
+            _lib.check(L.nr_edge_length_forward(_lib.ptr(vertices), _lib.ptr(topo.nbr_offsets), _lib.ptr(topo.nbr_index), B, V,
+                                                target_length, _lib.ptr(loss), _lib.ptr(ws), ws.numel(),
+                                                _lib.stream_of(vertices)), "nr_edge_length_forward")
+        ctx.topo, ctx.target_length = topo, target_length
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(vertices)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        vertices, = ctx.saved_tensors
+        topo = ctx.topo
+        g = grad_loss.to(torch.float32).contiguous()
+        gv = torch.empty_like(vertices)
+        with _lib.on_device(vertices.device):
+            _lib.check(_lib.lib().nr_edge_length_backward(_lib.ptr(vertices), _lib.ptr(topo.nbr_offsets), _lib.ptr(topo.nbr_index),
+                                                          _lib.ptr(g), vertices.shape[0], vertices.shape[1], ctx.target_length,
+                                                          _lib.ptr(gv), _lib.stream_of(vertices)), "nr_edge_length_backward")
+        return gv, None, None
+
+
+class CotLaplacianFunction(torch.autograd.Function):
+    """vertices [B, V, 3] float32 contiguous on the GPU -> loss [B].  When a gradient is needed the forward
+    saves delta [B, V, 3], the entry weights w [B, nnz] and winv [B, V]; the weights are constants of the
+    backward."""
+
+    @staticmethod
+    def forward(ctx, vertices, topo, eps):
+        B, V, F, nnz = vertices.shape[0], vertices.shape[1], topo.faces.shape[0], topo.nbr_index.numel()
+        dev = vertices.device
+        L = _lib.lib()
+        need = ctx.needs_input_grad[0]
+        corner_offsets, corners = topo.corner_csr()
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        delta = torch.empty_like(vertices) if need else None
+        w = torch.empty((B, nnz), dtype=torch.float32, device=dev) if need else None
+        winv = torch.empty((B, V), dtype=torch.float32, device=dev) if need else None
+        ws = torch.empty(L.nr_cot_laplacian_workspace_bytes(B, V, F), dtype=torch.uint8, device=dev)
+        with _lib.on_device(dev):
+            _lib.check(L.nr_cot_laplacian_forward(_lib.ptr(vertices), _lib.ptr(topo.faces), _lib.ptr(topo.nbr_offsets),
+                                                  _lib.ptr(topo.nbr_index), _lib.ptr(corner_offsets), _lib.ptr(corners), B, V, F,
+                                                  nnz, eps, _lib.ptr(delta), _lib.ptr(w), _lib.ptr(winv), _lib.ptr(loss),
+                                                  _lib.ptr(ws), ws.numel(), _lib.stream_of(vertices)),
+                       "nr_cot_laplacian_forward")
+        ctx.topo = topo
+        if need:
+            ctx.save_for_backward(delta, w, winv)
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        delta, w, winv = ctx.saved_tensors
+        topo = ctx.topo
+        g = grad_loss.to(torch.float32).contiguous()
+        gv = torch.empty_like(delta)
+        with _lib.on_device(delta.device):
+            _lib.check(_lib.lib().nr_cot_laplacian_backward(_lib.ptr(delta), _lib.ptr(w), _lib.ptr(winv),
+                                                            _lib.ptr(topo.nbr_offsets), _lib.ptr(topo.nbr_index), _lib.ptr(g),
+                                                            delta.shape[0], delta.shape[1], w.shape[1], _lib.ptr(gv),
+                                                            _lib.stream_of(delta)), "nr_cot_laplacian_backward")
+        return gv, None, None
+
+
 def laplacian_loss(vertices, faces, average=False):
     """sum_i |v_i - mean of i's neighbours|^2 per item: [B] for vertices [B, V, 3], a 0-dim tensor for
     [V, 3] or with average=True (the mean over the items).  `faces` is [F, 3] (shared by the items) or a
@@ -177,6 +312,31 @@ def flatten_loss(vertices, faces, eps=1e-6, average=False):
         return flatten_loss_torch(vertices, faces, eps, average)
     v, single, topo = _prepare(vertices, faces)
     return _finish(FlattenFunction.apply(v.contiguous(), topo, float(eps)), single, average)
+
+
+def edge_length_loss(vertices, faces, target_length=0.0, average=False):
+    """sum over the distinct undirected edges of (|v_i - v_j| - target_length)^2 per item (divide by
+    MeshTopology.num_all_edges for the mean form); target_length is a float >= 0.  Shapes, dispatch and
+    gradient as laplacian_loss; an edge of length 0 takes no gradient."""
+    target_length = float(target_length)
+    if not target_length >= 0.:
+        raise ValueError("target_length must not be negative")
+    if not _fused(vertices):
+        return edge_length_loss_torch(vertices, faces, target_length, average)
+    v, single, topo = _prepare(vertices, faces)
+    return _finish(EdgeLengthFunction.apply(v.contiguous(), topo, target_length), single, average)
+
+
+def cot_laplacian_loss(vertices, faces, eps=1e-12, average=False):
+    """sum_i |v_i - the cotangent-weighted mean of i's neighbours|^2 per item, the weights clamped at 0
+    per edge and a vertex whose weights sum to COT_MIN_WEIGHT or less left out (the module docstring has
+    the formulas).  The weights are recomputed from the vertices at every call but are constants of the
+    backward: no gradient flows through them.  Shapes, dispatch and gradient as laplacian_loss; a
+    MeshTopology passed as `faces` must know its faces (mesh_topology builds such a one)."""
+    if not _fused(vertices):
+        return cot_laplacian_loss_torch(vertices, faces, eps, average)
+    v, single, topo = _prepare(vertices, faces)
+    return _finish(CotLaplacianFunction.apply(v.contiguous(), topo, float(eps)), single, average)
 
 
 class LaplacianLoss(torch.nn.Module):
@@ -202,3 +362,29 @@ class FlattenLoss(torch.nn.Module):
 
     def forward(self, vertices):
         return flatten_loss(vertices, self.topology, self.eps, self.average)
+
+
+class EdgeLengthLoss(torch.nn.Module):
+    """edge_length_loss with the topology of `faces` held by the module."""
+
+    def __init__(self, faces, num_vertices, target_length=0.0, average=False):
+        super().__init__()
+        self.topology = mesh_topology(faces, num_vertices)
+        self.target_length = target_length
+        self.average = average
+
+    def forward(self, vertices):
+        return edge_length_loss(vertices, self.topology, self.target_length, self.average)
+
+
+class CotLaplacianLoss(torch.nn.Module):
+    """cot_laplacian_loss with the topology of `faces` held by the module."""
+
+    def __init__(self, faces, num_vertices, eps=1e-12, average=False):
+        super().__init__()
+        self.topology = mesh_topology(faces, num_vertices)
+        self.eps = eps
+        self.average = average
+
+    def forward(self, vertices):
+        return cot_laplacian_loss(vertices, self.topology, self.eps, self.average)

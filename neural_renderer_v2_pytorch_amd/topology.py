@@ -121,19 +121,27 @@ class MeshTopology:
       edges [E2, 4]                    rows (v0, v1, v2, v3) of the two-face edges, sorted by (v0, v1)
       edge_offsets [V + 1], edge_slots [4 E2]
                                        CSR vertex -> the entries 4 e + k with edges[e, k] == vertex, ascending
-    and the counts num_vertices, num_edges (E2), num_boundary_edges (one incident face) and
-    num_nonmanifold_edges (three or more)."""
+    and the counts num_vertices, num_edges (E2), num_boundary_edges (one incident face),
+    num_nonmanifold_edges (three or more) and num_all_edges (every distinct undirected edge).
+    A topology that knows its faces ([F, 3] int32 on its device, as mesh_topology builds it) also gives,
+    built on first use (corner_csr), what the cotangent Laplacian needs:
+      nbr_corner_offsets [nnz + 1], nbr_corners
+                                       CSR neighbour entry (i, j) -> the corners 3 f + k opposite the edge
+                                       {i, j} in `faces` as given, ascending; (i, j) and (j, i) hold the same list"""
     FIELDS = ("nbr_offsets", "nbr_index", "edges", "edge_offsets", "edge_slots")
 
-    def __init__(self, tensors, num_vertices, num_boundary_edges, num_nonmanifold_edges):
+    def __init__(self, tensors, num_vertices, num_boundary_edges, num_nonmanifold_edges, faces=None):
         for name, t in zip(self.FIELDS, tensors):
             setattr(self, name, t)
         self.num_vertices = int(num_vertices)
         self.num_edges = int(self.edges.shape[0])
         self.num_boundary_edges = int(num_boundary_edges)
         self.num_nonmanifold_edges = int(num_nonmanifold_edges)
+        self.num_all_edges = int(self.nbr_index.numel()) // 2
+        self.faces = faces
         self._on = {self.device: self}
-        self._index = None
+        self._host = {}  # shared by the copies on other devices: what corner_csr built on the host
+        self._index = self._edge_index = self._corners = self._cot_index = None
 
     @property
     def device(self):
@@ -150,8 +158,8 @@ class MeshTopology:
         hit = self._on.get(device)
         if hit is None:
             hit = MeshTopology([t.to(device) for t in self], self.num_vertices, self.num_boundary_edges,
-                               self.num_nonmanifold_edges)
-            hit._on = self._on
+                               self.num_nonmanifold_edges, None if self.faces is None else self.faces.to(device))
+            hit._on, hit._host = self._on, self._host
             self._on[device] = hit
         return hit
 
@@ -163,6 +171,66 @@ class MeshTopology:
             rows = torch.repeat_interleave(torch.arange(self.num_vertices, device=self.device), deg)
             self._index = (rows, self.nbr_index.long(), deg, self.edges.long())
         return self._index
+
+    def edge_index(self):
+        """int64 index tensors (i, j) of the distinct undirected edges: the neighbour entries with j > i."""
+        if self._edge_index is None:
+            rows, cols = self.composition_index()[:2]
+            once = rows < cols
+            self._edge_index = (rows[once], cols[once])
+        return self._edge_index
+
+    def corner_csr(self):
+        """(nbr_corner_offsets, nbr_corners) on this device: built on the host at the first call on any
+        device, copied once per device."""
+        if self._corners is None:
+            if self.faces is None:
+                raise ValueError("this topology was built without its faces: use mesh_topology(faces, num_vertices)")
+            if "corners" not in self._host:
+                self._host["corners"] = build_corner_csr(self.faces.cpu().numpy(), self.num_vertices,
+                                                         self.nbr_offsets.cpu().numpy(), self.nbr_index.cpu().numpy())
+            self._corners = tuple(torch.as_tensor(x, device=self.device) for x in self._host["corners"])
+        return self._corners
+
+    @property
+    def nbr_corner_offsets(self):
+        return self.corner_csr()[0]
+
+    @property
+    def nbr_corners(self):
+        return self.corner_csr()[1]
+
+    def cot_composition_index(self):
+        """int64 index tensors of the cotangent composition: the faces, and for every listed corner its
+        neighbour entry and itself."""
+        if self._cot_index is None:
+            off, corners = self.corner_csr()
+            count = (off[1:] - off[:-1]).long()
+            entry = torch.repeat_interleave(torch.arange(count.numel(), device=self.device), count)
+            self._cot_index = (self.faces.long(), entry, corners.long())
+        return self._cot_index
+
+
+def build_corner_csr(faces, V, nbr_offsets, nbr_index):
+    """(nbr_corner_offsets [nnz + 1], nbr_corners) int32 numpy, for faces [F, 3] as given and the neighbour
+    CSR build_topology made of them: corner 3 f + k is opposite the edge of face f's two other corners, and
+    is listed under both directions of that edge.  Faces with a repeated vertex have no corner listed."""
+    f = np.asarray(faces, np.int64).reshape(-1, 3)
+    if 3 * f.shape[0] >= 2 ** 31:
+        raise ValueError("mesh too large: 3 * F must stay below 2^31")
+    keep = np.flatnonzero((f[:, 0] != f[:, 1]) & (f[:, 1] != f[:, 2]) & (f[:, 0] != f[:, 2]))
+    f = f[keep]
+    a, b = f[:, [1, 2, 0]].reshape(-1), f[:, [2, 0, 1]].reshape(-1)
+    corner = (3 * keep[:, None] + np.arange(3)[None, :]).reshape(-1)
+    key, corner = np.concatenate([a * V + b, b * V + a]), np.concatenate([corner, corner])
+    if key.shape[0] >= 2 ** 31:
+        raise ValueError("mesh too large: the corner lists (6 per face) must stay below 2^31 entries")
+    order = np.lexsort((corner, key))  # by entry, ascending corners within one
+    rows = np.repeat(np.arange(V, dtype=np.int64), np.diff(np.asarray(nbr_offsets, np.int64)))
+    pair = rows * V + np.asarray(nbr_index, np.int64)  # ascending: the CSR's own order
+    entry = np.searchsorted(pair, key[order])
+    assert entry.size == 0 or np.array_equal(pair[entry], key[order])  # every face edge is a neighbour entry
+    return csr_offsets(entry, pair.shape[0]), corner[order].astype(np.int32)
 
 
 def build_topology(faces, V):
@@ -206,6 +274,6 @@ def mesh_topology(faces, num_vertices, device=None):
     topo = topologies.get(key)
     if topo is None:
         arrays, boundary, nonmanifold = build_topology(f.cpu().numpy(), V)
-        topo = MeshTopology([torch.as_tensor(x, device=f.device) for x in arrays], V, boundary, nonmanifold)
+        topo = MeshTopology([torch.as_tensor(x, device=f.device) for x in arrays], V, boundary, nonmanifold, f)
         topologies.put(key, topo, f)
     return topo

@@ -10,6 +10,9 @@ per step (events around each step) and graph-replay GPU time per step.  The JSON
 (fused not slower than the composition) and each kernel's algorithmic bytes.
 
     python tools/bench_mesh_loss.py [--steps 200] [--warmup 50] [--out FILE]
+
+--losses edge_cot times cot_laplacian_loss + 0.1 edge_length_loss (target: the mesh's mean edge length)
+instead, on the same meshes and in the same way (default --out profiles/mesh_regularizers_bench.jsonl).
 """
 import argparse
 import json
@@ -40,7 +43,19 @@ def kernel_bytes(B, V, E2, NN):
     }
 
 
-def cell(shape, path, warmup, steps):
+def kernel_bytes_edge_cot(B, V, F, NN):
+    """As kernel_bytes, for the edge-length and cotangent Laplacian kernels (corner lists: 6 F entries)."""
+    csr = (V + 1) + NN
+    return {
+        "k_edge_fwd": 4 * (B * V * 3 + csr + B * -(-V // 256)),
+        "k_edge_bwd": 4 * (B * V * 3 * 2 + csr + B),
+        "k_cot_face": 4 * (B * V * 3 + F * 3 + B * F * 3),
+        "k_cotlap_fwd<saved>": 4 * (B * V * 3 * 2 + csr + (NN + 1) + 6 * F + B * F * 3 + B * NN + B * V + B * -(-V // 256)),
+        "k_cotlap_bwd": 4 * (B * V * 3 * 2 + csr + B * NN + B * V + B),
+    }
+
+
+def cell(shape, path, warmup, steps, losses="laplacian_flatten"):
     import numpy as np
     import torch
     import neural_renderer_v2_pytorch_amd as nr
@@ -57,6 +72,13 @@ def cell(shape, path, warmup, steps):
         lap_fn, flat_fn = nr.laplacian_loss_torch, nr.flatten_loss_torch
     else:
         lap_fn, flat_fn = nr.laplacian_loss, nr.flatten_loss
+    if losses == "edge_cot":
+        rows, cols = topo.composition_index()[:2]
+        target = float((x.detach()[0, rows] - x.detach()[0, cols]).norm(dim=-1).mean())
+        edge_fn = nr.edge_length_loss_torch if path == "composition" else nr.edge_length_loss
+        lap_fn = nr.cot_laplacian_loss_torch if path == "composition" else nr.cot_laplacian_loss
+        flat_fn = lambda y, t: edge_fn(y, t, target)  # noqa: E731
+        topo.corner_csr()
 
     def note(what):
         print("[%s %s] %s" % (shape, path, what), file=sys.stderr, flush=True)
@@ -128,12 +150,20 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mesh_loss_bench.jsonl"))
+    ap.add_argument("--losses", choices=("laplacian_flatten", "edge_cot"), default="laplacian_flatten")
+    ap.add_argument("--out", default=None, help="default: profiles/mesh_loss_bench.jsonl, or "
+                    "profiles/mesh_regularizers_bench.jsonl with --losses edge_cot")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per cell")
     ap.add_argument("--cell", nargs=2, metavar=("SHAPE", "PATH"), help="run one cell in this process")
     a = ap.parse_args()
+    edge_cot = a.losses == "edge_cot"
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "mesh_regularizers_bench.jsonl" if edge_cot else "mesh_loss_bench.jsonl")
     if a.cell:
-        print(json.dumps(cell(a.cell[0], a.cell[1], a.warmup, a.steps)))
+        row = cell(a.cell[0], a.cell[1], a.warmup, a.steps, a.losses)
+        if edge_cot:
+            row["losses"] = a.losses
+        print(json.dumps(row))
         return 0
     rows = {}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -141,7 +171,7 @@ def main():
         for shape in SHAPES:
             for path in PATHS:
                 cmd = ["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--steps", str(a.steps),
-                       "--warmup", str(a.warmup), "--cell", shape, path]
+                       "--warmup", str(a.warmup), "--losses", a.losses, "--cell", shape, path]
                 p = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)
                 if p.returncode != 0:
                     print("cell %s %s ended with status %d: stopping" % (shape, path, p.returncode), file=sys.stderr)
@@ -158,7 +188,10 @@ def main():
                 summary["summary"]["%s/%s" % (shape, mode)] = {
                     "fused": fused[mode], "composition": comp[mode],
                     "speedup": round(comp[mode] / fused[mode], 2), "not_slower": fused[mode] <= comp[mode]}
-            summary["kernel_bytes"][shape] = kernel_bytes(fused["B"], fused["V"], fused["E2"], fused["neighbours"])
+            if edge_cot:
+                summary["kernel_bytes"][shape] = kernel_bytes_edge_cot(fused["B"], fused["V"], fused["F"], fused["neighbours"])
+            else:
+                summary["kernel_bytes"][shape] = kernel_bytes(fused["B"], fused["V"], fused["E2"], fused["neighbours"])
         line = json.dumps(summary)
         out.write(line + "\n")
         print(line)
