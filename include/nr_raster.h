@@ -394,6 +394,76 @@ NR_API int nr_cot_laplacian_backward(const float* delta, const float* w, const f
                                      int batch_size, int num_vertices, int num_neighbours, float* grad_vertices,
                                      void* stream);
 
+/* Articulated meshes (skinning.py): forward kinematics of a joint tree, then linear blend skinning.  A
+ * transform is 12 floats, row-major 3 x 4: [R | t].  No float atomics anywhere: every output and gradient is
+ * bitwise reproducible from run to run, and an item's results do not depend on the batch it is in.
+ *
+ * Skeleton: parents [J] int32, -1 a root (several allowed), else a joint index; joints need not be listed
+ * parents-first.  The host passes the joints sorted by depth -- level_joints [J], ascending within a level,
+ * level l being level_joints[level_offsets[l] .. level_offsets[l + 1]), level_offsets [L + 1] -- and the children
+ * CSR, child_offsets [J + 1] and children, ascending.  These arrays are trusted (topology.py builds them).
+ *
+ * Rotation: pose [B, J, 3] axis-angle (pose_is_matrix == 0) or [B, J, 3, 3] matrices, used as given.  For an
+ * axis-angle r with t2 = |r|^2, K = skew(r):  R = I + a K + b K^2,  a = sin t / t,  b = (1 - cos t) / t^2; where
+ * t2 < NR_RODRIGUES_SERIES, a = 1 - t2/6 + t2^2/120 and b = 1/2 - t2/24 + t2^2/720 (R and its gradient are
+ * defined at r = 0).
+ *
+ * Chain: c_j = joints[b or shared, j] (joints_batch_stride 0 or 3 J), p the parent of j:
+ *   root: G_j.R = R_j, G_j.t = c_j;   else: G_j.R = G_p.R R_j,  G_j.t = G_p.t + G_p.R (c_j - c_p)
+ *   posed_joints[b, j] = G_j.t;   transforms[b, j] = [G_j.R | G_j.t - G_j.R c_j]
+ * (a transform takes a rest-pose point to its posed place).
+ *
+ * Skinning: out[b, v] = sum_k w[v, k] (A.R x + A.t),  A = transforms[b, indices[v, k]],  x = vertices[b or
+ * shared, v] (vertices_batch_stride 0 or 3 V); weights and indices are [V, K], 1 <= K <= NR_SKIN_MAX_INFLUENCES,
+ * the weights used as given (not normalised).  A slot of weight 0 is padding; its index must still be in
+ * [0, J) (trusted).  The gradient to the transforms sums, per joint, over the slots of non-zero weight that
+ * name it: the joint CSR lists them by (vertex, slot) -- entry_vertex and entry_slot -- and the chunk table cuts
+ * each joint's row into runs of at most NR_SKIN_CHUNK entries: chunk c is the entries [chunk_begin[c],
+ * chunk_end[c]), and joint j owns the chunks [joint_chunk_offsets[j], joint_chunk_offsets[j + 1]), ascending.
+ *
+ * Limits (NR_ERR_ARGS otherwise): 1 <= J <= NR_SKIN_MAX_JOINTS for every call; for the nr_skin_* calls also
+ * 1 <= K <= NR_SKIN_MAX_INFLUENCES, B <= 65535 (an item is a grid row there) and 8 V < 2^31.  Pointers need the
+ * alignment of their element type only.  children may be NULL when no joint has a parent. */
+#define NR_SKIN_MAX_JOINTS 256
+#define NR_SKIN_MAX_INFLUENCES 8
+#define NR_SKIN_CHUNK 256
+#define NR_RODRIGUES_SERIES 1e-4f
+/* transforms [B, J, 3, 4] and posed_joints [B, J, 3], both fully written.  One block per item, one thread per
+ * joint, one barrier per level. */
+NR_API int nr_pose_transforms_forward(const float* pose, int pose_is_matrix, const float* joints,
+                                      long long joints_batch_stride, const int32_t* parents,
+                                      const int32_t* level_offsets, const int32_t* level_joints, int batch_size,
+                                      int num_joints, int num_levels, float* transforms, float* posed_joints,
+                                      void* stream);
+/* grad_transforms [B, J, 3, 4] and grad_posed_joints [B, J, 3] (either may be NULL: zeros) -> grad_pose (the
+ * pose's shape) and grad_joints [B, J, 3] (per item also for shared joints: the caller sums), each fully
+ * written or NULL.  transforms are the forward's. */
+NR_API int nr_pose_transforms_backward(const float* pose, int pose_is_matrix, const float* joints,
+                                       long long joints_batch_stride, const int32_t* parents,
+                                       const int32_t* level_offsets, const int32_t* level_joints,
+                                       const int32_t* child_offsets, const int32_t* children,
+                                       const float* transforms, const float* grad_transforms,
+                                       const float* grad_posed_joints, int batch_size, int num_joints,
+                                       int num_levels, float* grad_pose, float* grad_joints, void* stream);
+/* Scratch bytes of nr_skin_backward's transform gradient: the chunk partials [B][num_chunks][12]; no zero fill
+ * needed. */
+NR_API size_t nr_skin_workspace_bytes(int batch_size, int num_chunks);
+/* out [B, V, 3], fully written. */
+NR_API int nr_skin_forward(const float* vertices, long long vertices_batch_stride, const float* transforms,
+                           const float* weights, const int32_t* indices, int batch_size, int num_vertices,
+                           int num_joints, int num_influences, float* out, void* stream);
+/* grad_out [B, V, 3] -> grad_vertices ([B, V, 3], or [V, 3] for shared vertices: the sum over the items, in item
+ * order), grad_transforms [B, J, 3, 4] (exact zeros for a joint without entries; needs the joint CSR, the chunk
+ * table and the workspace) and grad_weights [V, K] (the sum over the items of g . (A x), for every slot); each
+ * fully written or NULL. */
+NR_API int nr_skin_backward(const float* vertices, long long vertices_batch_stride, const float* transforms,
+                            const float* weights, const int32_t* indices, const float* grad_out,
+                            const int32_t* entry_vertex, const int32_t* entry_slot, const int32_t* chunk_begin,
+                            const int32_t* chunk_end, const int32_t* joint_chunk_offsets, int batch_size,
+                            int num_vertices, int num_joints, int num_influences, int num_chunks,
+                            float* grad_vertices, float* grad_transforms, float* grad_weights, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* Image losses (image_loss.py): per-item reductions of images [B, N] float32, item b being the N
  * contiguous floats at images + b * image_stride (strides in elements, >= 0).  targets: item b at
  * targets + b * target_stride, 0 = one target shared by every item.  No float atomics: losses and

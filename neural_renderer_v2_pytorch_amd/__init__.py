@@ -30,5 +30,8 @@ from .point_loss import (ChamferLoss, MeshPointLoss, PointMeshLoss, chamfer_dist
                          closest_points_to_faces_torch, mesh_point_distance, mesh_point_distance_torch, nearest_points,
                          nearest_points_torch, point_mesh_distance, point_mesh_distance_torch, sample_points,
                          sample_points_torch)
+from .skinning import (NR_RODRIGUES_SERIES, NR_SKIN_CHUNK, NR_SKIN_MAX_INFLUENCES, NR_SKIN_MAX_JOINTS, Skeleton, SkinBinding,
+                       Skinning, pose_transforms, pose_transforms_torch, rodrigues_torch, skeleton, skin_binding,
+                       skin_vertices, skin_vertices_torch)
 
 __version__ = '2.0.2+mi355x.1'

@@ -65,6 +65,9 @@ NR_POINT_MESH_SPLIT_BLOCKS = 4096  # PM_SPLIT_BLOCKS: the faces are split over f
 NR_FACE_POINT_TILE, NR_FACE_POINT_FBLOCK = 64, 256  # csrc/nr_face_point.h FP_TILE (points in LDS), FP_FBLOCK (faces per block)
 NR_FACE_POINT_SPLIT_BLOCKS = 4096  # FP_SPLIT_BLOCKS: the points are split over further blocks while a launch has fewer
 NR_COT_MIN_WEIGHT = 1e-6  # include/nr_raster.h: a vertex whose cotangent weights sum to no more has delta = 0
+# include/nr_raster.h: joints of a skeleton, influences per vertex, entries of a joint's CSR row per block of
+# k_skin_bwd_transforms, and the |r|^2 below which Rodrigues' coefficients come from their series
+NR_SKIN_MAX_JOINTS, NR_SKIN_MAX_INFLUENCES, NR_SKIN_CHUNK, NR_RODRIGUES_SERIES = 256, 8, 256, 1e-4
 
 
 class NrCameraArgs(ctypes.Structure):  # include/nr_raster.h
@@ -154,6 +157,12 @@ SIGNATURES = {
     "nr_cot_laplacian_forward": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, c_size_t,
                                          _P]),
     "nr_cot_laplacian_backward": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
+    "nr_pose_transforms_forward": (c_int, [_P, c_int, _P, c_ll, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "nr_pose_transforms_backward": (c_int, [_P, c_int, _P, c_ll, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
+    "nr_skin_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "nr_skin_forward": (c_int, [_P, c_ll, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "nr_skin_backward": (c_int, [_P, c_ll, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P,
+                                 c_size_t, _P]),
     "nr_image_loss_workspace_bytes": (c_size_t, [c_int, c_int]),
     "nr_pointwise_loss_forward": (c_int, _pointwise + [_P, _P, c_size_t, _P]),
     "nr_pointwise_loss_backward": (c_int, _pointwise + [_P, _P, _P]),
@@ -201,7 +210,8 @@ def lib():
                            "__graft_entry__.build() (there is no CPU fallback)" % LIB_PATH)
     L = ctypes.CDLL(LIB_PATH)
     # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_ssim_loss_*, nr_adam_*, nr_attributes_*,
-    # point-loss entry points and the two point / mesh distance directions, nr_point_mesh_* and nr_face_point_*):
+    # point-loss entry points, the two point / mesh distance directions, nr_point_mesh_* and nr_face_point_*, and the
+    # articulated-mesh entry points, nr_pose_transforms_* and nr_skin_*):
     # a library built before them still reports the version this binding expects
     missing = [name for name in EXPORTS if not hasattr(L, name)]
     if missing:

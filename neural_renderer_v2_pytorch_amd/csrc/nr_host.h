@@ -130,6 +130,16 @@ CotLayout cot_layout(int B, int V, int F) {
     return {c.take((size_t)B * (((size_t)V + ML_BLOCK - 1) / ML_BLOCK) * 4), c.take((size_t)B * F * 3 * 4), c.off};
 }
 
+// skinning backward (nr_skinning.h): the chunk partials [B][num_chunks][12] k_skin_bwd_transforms leaves for
+// k_skin_sum
+struct SkinLayout {
+    size_t partial, total;
+};
+SkinLayout skin_layout(int B, int num_chunks) {
+    Cutter c;
+    return {c.take((size_t)B * num_chunks * 12 * 4), c.off};
+}
+
 // How a nearest-neighbour launch (a chamfer direction: PL_*, a PairDir: PM_* or FP_*) is cut: query blocks per
 // item, and target ranges per query block (more than one -- the split path -- while the launch has fewer
 // than split_blocks blocks and every range still holds at least a full tile of targets: few queries against

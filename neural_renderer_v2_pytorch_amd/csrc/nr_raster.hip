@@ -27,7 +27,8 @@
 // perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian, cotangent
 // Laplacian, flatten and edge-length regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_ssim_loss.h (SSIM image loss), nr_adam.h
 // (multi-tensor Adam), nr_attributes.h (per-vertex attribute rendering), nr_point_loss.h (chamfer distance,
-// nearest points and surface sampling), nr_point_mesh.h (point-to-surface distance), nr_face_point.h (face-to-scan distance), nr_host.h (workspace layouts, launch helpers, argument checks); this file holds the extern "C" ABI.
+// nearest points and surface sampling), nr_point_mesh.h (point-to-surface distance), nr_face_point.h (face-to-scan distance),
+// nr_skinning.h (forward kinematics and linear blend skinning), nr_host.h (workspace layouts, launch helpers, argument checks); this file holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -67,6 +68,7 @@
 #include "nr_point_loss.h"
 #include "nr_point_mesh.h"
 #include "nr_face_point.h"
+#include "nr_skinning.h"
 #include "nr_host.h"
 
 
@@ -1006,6 +1008,132 @@ int nr_cot_laplacian_backward(const float* delta, const float* w, const float* w
     nr_launch(k_cotlap_bwd, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, (hipStream_t)stream, delta, w, winv, nbr_offsets,
               nbr_index, grad_loss, V, nnz, nblk, grad_vertices);
     return check_launch("k_cotlap_bwd");
+}
+
+// ---- articulated meshes (nr_skinning.h) ----
+static int validate_pose(int B, int J, int L, long long joints_bstride) {
+    if (B < 0) return fail(NR_ERR_ARGS, "bad batch size B=%d", B);
+    if (J < 1 || J > NR_SKIN_MAX_JOINTS) return fail(NR_ERR_ARGS, "bad joint count J=%d (1 to %d)", J, NR_SKIN_MAX_JOINTS);
+    if (L < 1 || L > J) return fail(NR_ERR_ARGS, "bad level count L=%d for J=%d joints", L, J);
+    if (joints_bstride != 0 && joints_bstride != (long long)J * 3)
+        return fail(NR_ERR_ARGS, "joints_batch_stride %lld is neither 0 nor 3 J = %d", joints_bstride, J * 3);
+    return NR_OK;
+}
+
+int nr_pose_transforms_forward(const float* pose, int pose_is_matrix, const float* joints, long long joints_batch_stride,
+                               const int32_t* parents, const int32_t* level_offsets, const int32_t* level_joints, int batch_size,
+                               int num_joints, int num_levels, float* transforms, float* posed_joints, void* stream) {
+    const int B = batch_size, J = num_joints, L = num_levels;
+    int e = validate_pose(B, J, L, joints_batch_stride);
+    if (e) return e;
+    if (!pose || !joints || !parents || !level_offsets || !level_joints) return fail(NR_ERR_ARGS, "null pose, joints or skeleton");
+    if (!transforms || !posed_joints) return fail(NR_ERR_ARGS, "null transforms or posed_joints");
+    if (B == 0) return NR_OK;
+    nr_launch(k_pose_fwd, dim3((unsigned)B), dim3(SK_BLOCK), 0, (hipStream_t)stream, pose, pose_is_matrix ? 1 : 0, joints,
+              joints_batch_stride, parents, level_offsets, level_joints, J, L, transforms, posed_joints);
+    return check_launch("k_pose_fwd");
+}
+
+int nr_pose_transforms_backward(const float* pose, int pose_is_matrix, const float* joints, long long joints_batch_stride,
+                                const int32_t* parents, const int32_t* level_offsets, const int32_t* level_joints,
+                                const int32_t* child_offsets, const int32_t* children, const float* transforms,
+                                const float* grad_transforms, const float* grad_posed_joints, int batch_size, int num_joints,
+                                int num_levels, float* grad_pose, float* grad_joints, void* stream) {
+    const int B = batch_size, J = num_joints, L = num_levels;
+    int e = validate_pose(B, J, L, joints_batch_stride);
+    if (e) return e;
+    if (!pose || !joints || !parents || !level_offsets || !level_joints) return fail(NR_ERR_ARGS, "null pose, joints or skeleton");
+    // children may be NULL: a forest of roots alone has no child, and the kernel reads the list only inside a row
+    if (!child_offsets) return fail(NR_ERR_ARGS, "null child_offsets");
+    if (!transforms) return fail(NR_ERR_ARGS, "null transforms");
+    if (!grad_pose && !grad_joints) return fail(NR_ERR_ARGS, "no gradient requested");
+    if (B == 0) return NR_OK;
+    nr_launch(k_pose_bwd, dim3((unsigned)B), dim3(SK_BLOCK), 0, (hipStream_t)stream, pose, pose_is_matrix ? 1 : 0, joints,
+              joints_batch_stride, parents, level_offsets, level_joints, child_offsets, children, transforms, grad_transforms,
+              grad_posed_joints, J, L, grad_pose, grad_joints);
+    return check_launch("k_pose_bwd");
+}
+
+static int validate_skin(int B, int V, int J, int K, long long v_bstride) {
+    if (B < 0 || V < 0) return fail(NR_ERR_ARGS, "bad sizes B=%d V=%d", B, V);
+    if (B > 65535) return fail(NR_ERR_ARGS, "too many items B=%d (at most 65535)", B);
+    if (J < 1 || J > NR_SKIN_MAX_JOINTS) return fail(NR_ERR_ARGS, "bad joint count J=%d (1 to %d)", J, NR_SKIN_MAX_JOINTS);
+    if (K < 1 || K > NR_SKIN_MAX_INFLUENCES)
+        return fail(NR_ERR_ARGS, "bad influence count K=%d (1 to %d)", K, NR_SKIN_MAX_INFLUENCES);
+    if (V > INT_MAX / NR_SKIN_MAX_INFLUENCES) return fail(NR_ERR_ARGS, "too many vertices V=%d (8 V must stay below 2^31)", V);
+    if (v_bstride != 0 && v_bstride != (long long)V * 3)
+        return fail(NR_ERR_ARGS, "vertices_batch_stride %lld is neither 0 nor 3 V = %lld", v_bstride, (long long)V * 3);
+    return NR_OK;
+}
+
+size_t nr_skin_workspace_bytes(int batch_size, int num_chunks) {
+    if (batch_size <= 0 || num_chunks <= 0) return 0;
+    return skin_layout(batch_size, num_chunks).total;
+}
+
+int nr_skin_forward(const float* vertices, long long vertices_batch_stride, const float* transforms, const float* weights,
+                    const int32_t* indices, int batch_size, int num_vertices, int num_joints, int num_influences, float* out,
+                    void* stream) {
+    const int B = batch_size, V = num_vertices, J = num_joints, K = num_influences;
+    int e = validate_skin(B, V, J, K, vertices_batch_stride);
+    if (e) return e;
+    if (B == 0 || V == 0) return NR_OK;
+    if (!vertices || !transforms || !weights || !indices || !out) return fail(NR_ERR_ARGS, "null pointer");
+    nr_launch(k_skin_fwd, grid_1d(V, SK_BLOCK, B), dim3(SK_BLOCK), 0, (hipStream_t)stream, vertices, vertices_batch_stride,
+              transforms, weights, indices, V, J, K, out);
+    return check_launch("k_skin_fwd");
+}
+
+int nr_skin_backward(const float* vertices, long long vertices_batch_stride, const float* transforms, const float* weights,
+                     const int32_t* indices, const float* grad_out, const int32_t* entry_vertex, const int32_t* entry_slot,
+                     const int32_t* chunk_begin, const int32_t* chunk_end, const int32_t* joint_chunk_offsets, int batch_size,
+                     int num_vertices, int num_joints, int num_influences, int num_chunks, float* grad_vertices,
+                     float* grad_transforms, float* grad_weights, void* workspace, size_t workspace_bytes, void* stream) {
+    const int B = batch_size, V = num_vertices, J = num_joints, K = num_influences, NC = num_chunks;
+    int e = validate_skin(B, V, J, K, vertices_batch_stride);
+    if (e) return e;
+    if (NC < 0) return fail(NR_ERR_ARGS, "bad chunk count %d", NC);
+    if (!grad_vertices && !grad_transforms && !grad_weights) return fail(NR_ERR_ARGS, "no gradient requested");
+    if (V > 0 && (!vertices || !transforms || !weights || !indices || !grad_out)) return fail(NR_ERR_ARGS, "null pointer");
+    if (grad_transforms) {
+        if (!joint_chunk_offsets) return fail(NR_ERR_ARGS, "grad_transforms without joint_chunk_offsets");
+        if (NC > 0 && (V == 0 || !entry_vertex || !entry_slot || !chunk_begin || !chunk_end))
+            return fail(NR_ERR_ARGS, "chunks without vertices, the joint CSR or the chunk table");
+        if (B > 0 && NC > 0 && (!workspace || workspace_bytes < skin_layout(B, NC).total))
+            return fail(NR_ERR_WORKSPACE, "skinning workspace missing or too small");
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const bool shared = vertices_batch_stride == 0;
+    if (B == 0) {  // the sums over an empty batch
+        if (V > 0 && grad_weights && !zero_async(grad_weights, (size_t)V * K * 4, st, &e)) return e;
+        if (V > 0 && grad_vertices && shared && !zero_async(grad_vertices, (size_t)V * 3 * 4, st, &e)) return e;
+        return NR_OK;
+    }
+    if (V > 0 && (grad_vertices || grad_weights)) {
+        if (grad_weights || shared) {
+            nr_launch(k_skin_bwd_vertices<true>, grid_1d(V, SK_BLOCK), dim3(SK_BLOCK), 0, st, vertices, vertices_batch_stride,
+                      transforms, weights, indices, grad_out, B, V, J, K, grad_vertices, grad_weights);
+        } else {
+            nr_launch(k_skin_bwd_vertices<false>, grid_1d(V, SK_BLOCK, B), dim3(SK_BLOCK), 0, st, vertices,
+                      vertices_batch_stride, transforms, weights, indices, grad_out, B, V, J, K, grad_vertices, grad_weights);
+        }
+        e = check_launch("k_skin_bwd_vertices");
+        if (e) return e;
+    }
+    if (grad_transforms) {
+        float* partial = NC > 0 ? (float*)((char*)workspace + skin_layout(B, NC).partial) : nullptr;
+        if (NC > 0) {
+            nr_launch(k_skin_bwd_transforms, dim3((unsigned)NC, (unsigned)B), dim3(SK_BLOCK), 0, st, vertices,
+                      vertices_batch_stride, weights, grad_out, entry_vertex, entry_slot, chunk_begin, chunk_end, V, K, partial);
+            e = check_launch("k_skin_bwd_transforms");
+            if (e) return e;
+        }
+        const long long n = (long long)B * J * 12;
+        nr_launch(k_skin_sum, grid_1d(n, SK_BLOCK), dim3(SK_BLOCK), 0, st, (const float*)partial, joint_chunk_offsets, n, J, NC,
+                  grad_transforms);
+        return check_launch("k_skin_sum");
+    }
+    return NR_OK;
 }
 
 // ---- point losses (nr_point_loss.h) ----

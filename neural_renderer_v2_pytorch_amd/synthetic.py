@@ -60,6 +60,40 @@ def torus(nu=250, nv=100, major=0.65, minor=0.25):
     return v, f.astype(np.int32)
 
 
+def rigged_tube(rings=16, segments=12, joints=4, radius=0.2, height=1.2):
+    """A capped tube along y with a chain of `joints` joints on its axis: (vertices [V, 3] float32, faces
+    [F, 3] int32 wound outwards, joint positions [J, 3] float32, parents [J] int32, weights [V, 2] float32,
+    indices [V, 2] int32).  V = rings * segments + 2 (the cap centres last), F = 2 segments rings.  Joint j sits
+    at y = -height / 2 + j height / joints with joint j - 1 its parent; a vertex between joints j and j + 1 is
+    weighted linearly between the two (K = 2), one above the last joint follows that joint alone (its second
+    slot is padding of weight 0)."""
+    if rings < 2 or segments < 3 or joints < 1:
+        raise ValueError("rigged_tube needs rings >= 2, segments >= 3 and joints >= 1")
+    ys = -height / 2 + height * np.arange(rings) / (rings - 1)
+    ang = np.arange(segments) * (2 * math.pi / segments)
+    ring = np.stack([radius * np.cos(ang), np.zeros(segments), radius * np.sin(ang)], -1)
+    v = (ring[None] + np.stack([np.zeros(rings), ys, np.zeros(rings)], -1)[:, None]).reshape(-1, 3)
+    v = np.concatenate([v, [[0, -height / 2, 0], [0, height / 2, 0]]])
+    i, j = np.arange(rings - 1)[:, None], np.arange(segments)[None, :]
+    a, b = i * segments + j, i * segments + (j + 1) % segments
+    c, d = a + segments, b + segments
+    side = np.concatenate([np.stack([a, c, b], -1).reshape(-1, 3), np.stack([b, c, d], -1).reshape(-1, 3)])
+    s, top = np.arange(segments), (rings - 1) * segments
+    bottom_c, top_c = rings * segments, rings * segments + 1
+    caps = np.concatenate([np.stack([np.full(segments, bottom_c), s, (s + 1) % segments], -1),
+                           np.stack([np.full(segments, top_c), top + (s + 1) % segments, top + s], -1)])
+    f = np.concatenate([side, caps]).astype(np.int32)
+    jy = -height / 2 + height * np.arange(joints) / joints
+    c_j = np.stack([np.zeros(joints), jy, np.zeros(joints)], -1)
+    parents = np.arange(joints, dtype=np.int32) - 1
+    pos = np.clip((v[:, 1] + height / 2) / (height / joints), 0, None)  # in bone lengths above joint 0
+    lo = np.minimum(pos.astype(np.int64), joints - 1)
+    frac = np.where(lo < joints - 1, pos - lo, 0.)
+    indices = np.stack([lo, np.minimum(lo + 1, joints - 1)], -1).astype(np.int32)
+    weights = np.stack([1 - frac, frac], -1)
+    return (v.astype(np.float32), f, c_j.astype(np.float32), parents, weights.astype(np.float32), indices)
+
+
 def subdivide(v, f, vt=None, ft=None):
     """Midpoint subdivision: every triangle into 4 (shared edge midpoints, computed in float64);
     the same on the uv mesh when given.  SURVEY.md section 8d: the car 4e49873... (F=3644) once

@@ -1,14 +1,17 @@
 """What the package derives on the host from an index tensor (faces [F, 3], faces_textures,
 faces_attributes), and the caches that make it a once-per-tensor cost: the range check (faces_i32),
-the CSR lists the backward gathers walk (vertex_adjacency, normal_adjacency) and the mesh losses'
-MeshTopology.  Every list is built with stable sorts, so each has one fixed, ascending order: the
-summation order of every gather that walks it, which keeps those sums reproducible bit for bit.
+the CSR lists the backward gathers walk (vertex_adjacency, normal_adjacency), the mesh losses'
+MeshTopology, and what skinning.py derives from a rig's parents and weights (Skeleton, SkinBinding).
+Every list is built with stable sorts, so each has one fixed, ascending order: the summation order
+of every gather that walks it, which keeps those sums reproducible bit for bit.
 A steady-state call (the same device int32 tensor again) is one key tuple and one cache lookup: no
 device-to-host copy and no host synchronisation, so such a step can be captured in a HIP graph."""
 import collections
 
 import numpy as np
 import torch
+
+from . import _lib
 
 
 class TensorCache:
@@ -257,6 +260,236 @@ def build_topology(faces, V):
     edge_offsets, edge_slots = csr(edges.reshape(-1), V)
     arrays = [csr_offsets(pair // W, V), pair % W, edges, edge_offsets, edge_slots]
     return [x.astype(np.int32) for x in arrays], int((count == 1).sum()), int((count > 2).sum())
+
+
+def _device_of(device):
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
+class _PerDevice:
+    """int32 / float32 tensors named by FIELDS on one device, copied once per further device (`to`)."""
+    FIELDS = ()
+
+    def _place(self, tensors):
+        for name, t in zip(self.FIELDS, tensors):
+            setattr(self, name, t)
+        self._on = {self.device: self}
+
+    @property
+    def device(self):
+        return getattr(self, self.FIELDS[0]).device
+
+    def to(self, device):
+        """This structure on `device` (copied once per device)."""
+        device = _device_of(device)
+        hit = self._on.get(device)
+        if hit is None:
+            hit = object.__new__(type(self))
+            hit.__dict__.update(self.__dict__)
+            for name in self.FIELDS:
+                setattr(hit, name, getattr(self, name).to(device))
+            self._on[device] = hit
+        return hit
+
+
+# ---- articulated meshes (skinning.py) ----
+SKIN_MAX_JOINTS, SKIN_MAX_INFLUENCES, SKIN_CHUNK = _lib.NR_SKIN_MAX_JOINTS, _lib.NR_SKIN_MAX_INFLUENCES, _lib.NR_SKIN_CHUNK
+skeletons, bindings = TensorCache(), TensorCache()
+
+
+def build_skeleton(parents):
+    """(level_offsets [L + 1], level_joints [J], child_offsets [J + 1], children) int32 numpy of parents [J]:
+    the joints sorted by depth (ascending within a level) and the children CSR (ascending).  -1 marks a root;
+    a cycle, an index outside [0, J) or J outside [1, SKIN_MAX_JOINTS] is a ValueError."""
+    p = np.asarray(parents)
+    if p.ndim != 1 or p.dtype.kind not in "iu":
+        raise ValueError("parents must be a [J] integer tensor or array")
+    p = p.astype(np.int64)
+    J = p.shape[0]
+    if J < 1 or J > SKIN_MAX_JOINTS:
+        raise ValueError("a skeleton has 1 to %d joints, got %d" % (SKIN_MAX_JOINTS, J))
+    bad = np.flatnonzero((p < -1) | (p >= J))
+    if bad.size:
+        raise ValueError("parents[%d] = %d is neither -1 nor a joint index in [0, %d)" % (bad[0], p[bad[0]], J))
+    depth = np.where(p < 0, 0, -1)
+    level = 0
+    while True:  # a level per pass: the joints whose parent was placed by the pass before
+        level += 1
+        new = (depth < 0) & (depth[np.maximum(p, 0)] == level - 1)
+        if not new.any():
+            break
+        depth[new] = level
+    if (depth < 0).any():
+        raise ValueError("parents hold a cycle (through joint %d)" % int(np.flatnonzero(depth < 0)[0]))
+    level_offsets, level_joints = csr(depth, level)
+    has = np.flatnonzero(p >= 0)
+    child_offsets, order = csr(p[has], J)
+    return level_offsets, level_joints.astype(np.int32), child_offsets, has[order].astype(np.int32)
+
+
+class Skeleton(_PerDevice):
+    """A joint tree (or forest), as int32 tensors on one device:
+      parents [J]                       -1 for a root, else the parent's index; joints need not be parents-first
+      level_offsets [L + 1], level_joints [J]
+                                        the joints sorted by depth, ascending within a level
+      child_offsets [J + 1], children   CSR joint -> its children, ascending
+    and num_joints, num_levels, plus the host lists `parent_list` and `order` (level_joints) the torch
+    composition walks.  Skeleton(parents) builds one from any [J] integer tensor, array or list; the functions
+    of skinning.py go through skeleton(), which caches."""
+    FIELDS = ("parents", "level_offsets", "level_joints", "child_offsets", "children")
+
+    def __init__(self, parents, device=None):
+        if isinstance(parents, Skeleton):
+            self.__dict__.update(parents.to(parents.device if device is None else device).__dict__)
+            return
+        if device is None:
+            device = parents.device if torch.is_tensor(parents) else torch.device("cpu")
+        host = parents.detach().cpu().numpy() if torch.is_tensor(parents) else np.asarray(parents)
+        arrays = build_skeleton(host)
+        self.parent_list = [int(x) for x in host]
+        self.order = [int(x) for x in arrays[1]]
+        self.num_joints, self.num_levels = len(self.parent_list), int(arrays[0].shape[0]) - 1
+        dev = _device_of(device)
+        self._place([torch.as_tensor(x, device=dev) for x in (host.astype(np.int32),) + arrays])
+
+
+def skeleton(parents, device=None):
+    """The Skeleton of `parents` on `device` (default: the tensor's own, the CPU for arrays): a Skeleton is moved,
+    a tensor is looked up by (storage, version) -- no device-to-host copy on a hit -- and an array or list by its
+    values."""
+    if isinstance(parents, Skeleton):
+        return parents if device is None else parents.to(device)
+    if torch.is_tensor(parents):
+        key = TensorCache.key(parents)
+    else:
+        key = ("values", tuple(int(x) for x in np.asarray(parents).reshape(-1)))
+    hit = skeletons.get(key)
+    if hit is None:
+        hit = Skeleton(parents)
+        skeletons.put(key, hit, parents)
+    return hit if device is None else hit.to(device)
+
+
+def build_binding(weights, indices, num_joints):
+    """The arrays of SkinBinding (numpy) from weights [V, K] with indices [V, K], or from dense weights [V, J]
+    (indices None): (indices, weights, joint_offsets, entry_vertex, entry_slot, chunk_joint, chunk_begin,
+    chunk_end, joint_chunk_offsets)."""
+    w = np.ascontiguousarray(np.asarray(weights, np.float32))
+    if w.ndim != 2:
+        raise ValueError("weights must be [V, K] with indices, or dense [V, J]")
+    V = w.shape[0]
+    if indices is None:
+        J = w.shape[1] if num_joints is None else int(num_joints)
+        if w.shape[1] != J:
+            raise ValueError("dense weights must be [V, %d], got %s" % (J, list(w.shape)))
+        nz = w != 0
+        count = nz.sum(1)
+        over = np.flatnonzero(count > SKIN_MAX_INFLUENCES)
+        if over.size:
+            raise ValueError("row %d of the weights has %d non-zero entries; at most %d joints may influence a vertex"
+                             % (over[0], count[over[0]], SKIN_MAX_INFLUENCES))
+        K = max(int(count.max()) if V else 1, 1)
+        # a row's non-zero columns first, ascending (stable), then zero columns: padding of weight 0
+        idx = np.argsort(~nz, axis=1, kind="stable")[:, :K]
+        w = np.take_along_axis(w, idx, 1)
+    else:
+        idx = np.asarray(indices)
+        if idx.dtype.kind not in "iu" or idx.shape != w.shape:
+            raise ValueError("indices must be integers of the weights' shape %s, got %s %s" % (list(w.shape), idx.dtype, list(idx.shape)))
+        if num_joints is None:
+            raise ValueError("weights with indices need num_joints")
+        J, K = int(num_joints), w.shape[1]
+        if K < 1 or K > SKIN_MAX_INFLUENCES:
+            raise ValueError("a vertex takes 1 to %d influences, got K = %d" % (SKIN_MAX_INFLUENCES, K))
+        idx = idx.astype(np.int64)
+        if idx.size and (idx.min() < 0 or idx.max() >= J):
+            raise ValueError("indices out of range [0, %d): min %d max %d" % (J, idx.min(), idx.max()))
+    if J < 1 or J > SKIN_MAX_JOINTS:
+        raise ValueError("a skeleton has 1 to %d joints, got %d" % (SKIN_MAX_JOINTS, J))
+    if V * K >= 2 ** 31:
+        raise ValueError("mesh too large: V * K must stay below 2^31")
+    idx = np.ascontiguousarray(idx.astype(np.int32))
+    # the joint CSR: the slots of non-zero weight, by (vertex, slot) within a joint (a stable sort of the flat order)
+    slots = np.flatnonzero(w.reshape(-1) != 0)
+    joint = idx.reshape(-1)[slots].astype(np.int64)
+    joint_offsets, order = csr(joint, J)
+    entries = slots[order]
+    # the chunk table: each non-empty row cut into runs of at most SKIN_CHUNK entries
+    rows = np.diff(joint_offsets.astype(np.int64))
+    chunks = -(-rows // SKIN_CHUNK)
+    joint_chunk_offsets = np.zeros(J + 1, np.int32)
+    np.cumsum(chunks, out=joint_chunk_offsets[1:])
+    chunk_joint = np.repeat(np.arange(J, dtype=np.int64), chunks)
+    local = np.arange(chunk_joint.shape[0], dtype=np.int64) - joint_chunk_offsets[chunk_joint]
+    chunk_begin = joint_offsets[chunk_joint] + local * SKIN_CHUNK
+    chunk_end = np.minimum(chunk_begin + SKIN_CHUNK, joint_offsets[chunk_joint + 1])
+    i32 = [x.astype(np.int32) for x in (joint_offsets, entries // K, entries % K, chunk_joint, chunk_begin, chunk_end,
+                                        joint_chunk_offsets)]
+    return (idx, w, *i32)
+
+
+class SkinBinding(_PerDevice):
+    """Skinning weights in the form the fused kernels read, on one device:
+      indices [V, K] int32, weights [V, K] float32
+                                        from a dense [V, J] matrix: each row's non-zero entries in ascending joint
+                                        order, K the largest row count (at least 1), padded with slots of weight 0
+      joint_offsets [J + 1], entry_vertex, entry_slot
+                                        CSR joint -> the slots (vertex, slot) of non-zero weight that name it, ordered
+                                        by (vertex, slot): zero-weight padding appears in no row
+      chunk_joint, chunk_begin, chunk_end, joint_chunk_offsets [J + 1]
+                                        the rows cut into runs of at most SKIN_CHUNK entries; a row of 0 entries has none
+    and num_vertices, num_joints, num_influences (K), num_entries, num_chunks.  chunk_joint stays on the host (the
+    kernels find a joint's chunks through joint_chunk_offsets).  skin_binding() builds and caches one."""
+    FIELDS = ("indices", "weights", "joint_offsets", "entry_vertex", "entry_slot", "chunk_begin", "chunk_end",
+              "joint_chunk_offsets")
+
+    def __init__(self, arrays, num_joints, device):
+        indices, weights, joint_offsets, entry_vertex, entry_slot, chunk_joint, chunk_begin, chunk_end, jco = arrays
+        dev = _device_of(device)
+        self._place([torch.as_tensor(x, device=dev) for x in (indices, weights, joint_offsets, entry_vertex, entry_slot,
+                                                              chunk_begin, chunk_end, jco)])
+        self.chunk_joint = torch.as_tensor(chunk_joint)
+        self.num_vertices, self.num_influences = int(indices.shape[0]), int(indices.shape[1])
+        self.num_joints = int(num_joints)
+        self.num_entries, self.num_chunks = int(entry_vertex.shape[0]), int(chunk_begin.shape[0])
+        self._gather = {}
+
+    def gather_index(self):
+        """(indices as int64, the mask of the slots of non-zero weight as float32) on this device: what reads a
+        live dense matrix into the [V, K] form."""
+        hit = self._gather.get(self.device)
+        if hit is None:
+            hit = self._gather[self.device] = (self.indices.long(), (self.weights != 0).to(torch.float32))
+        return hit
+
+
+def skin_binding(weights, indices=None, num_joints=None, device=None):
+    """The SkinBinding of dense weights [V, J], or of weights [V, K] with integer indices [V, K] and num_joints, on
+    `device` (default: the weights' own, the CPU for arrays).  More than SKIN_MAX_INFLUENCES non-zero entries in a
+    row, an index outside [0, num_joints) or mismatched shapes raise ValueError.  Tensors are looked up by
+    (storage, version) of both, so a steady-state call is one key and one lookup -- no device-to-host copy -- and an
+    in-place edit (an optimiser's step on learned weights) rebuilds the binding at the next call."""
+    if isinstance(weights, SkinBinding):
+        return weights if device is None else weights.to(device)
+    tensors = torch.is_tensor(weights) and (indices is None or torch.is_tensor(indices))
+    if tensors:
+        key = (TensorCache.key(weights, None if num_joints is None else int(num_joints)),
+               None if indices is None else TensorCache.key(indices), tuple(weights.shape))
+        hit = bindings.get(key)
+    else:
+        hit = None
+    if hit is None:
+        host = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else x  # noqa: E731
+        w, idx = host(weights), None if indices is None else host(indices)
+        arrays = build_binding(w, idx, num_joints)
+        J = np.asarray(w).shape[1] if indices is None else int(num_joints)
+        hit = SkinBinding(arrays, J, weights.device if torch.is_tensor(weights) else "cpu")
+        if tensors:
+            bindings.put(key, hit, weights, indices)
+    return hit if device is None else hit.to(device)
 
 
 def mesh_topology(faces, num_vertices, device=None):
