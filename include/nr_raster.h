@@ -394,6 +394,50 @@ NR_API int nr_cot_laplacian_backward(const float* delta, const float* w, const f
                                      int batch_size, int num_vertices, int num_neighbours, float* grad_vertices,
                                      void* stream);
 
+/* As-rigid-as-possible (ARAP) energy (mesh_loss.py: arap_loss), on the same neighbour CSR and the same
+ * conventions: how far the deformed vertices q [B, V, 3] are from being, around every vertex, a rotated copy
+ * of the rest shape p.  p and the entry weights w are read at an item stride each, 0 when the items share
+ * them (else 3 V and nnz).  With e_ij = p_i - p_j and d_ij = q_i - q_j:
+ *   S_i  = sum_{j in N(i)} w_ij e_ij d_ij^T   (3 x 3, the neighbours in CSR order)
+ *   R_i  = the rotation (det +1) that maximises tr(R S_i): with S = U Sigma V^T it is
+ *          V diag(1, 1, det(V U^T)) U^T.  S_i = 0 gives R_i = I.  Where the maximiser is not unique (the two
+ *          largest eigenvalues of Horn's 4 x 4 matrix meet: sigma_2 + det sigma_3 = 0) any maximiser is
+ *          returned; every output stays finite.
+ *   loss_b = sum_i sum_{j in N(i)} w_ij |d_ij - R_i e_ij|^2
+ * The rotations are constants of the backward; they maximise, so by the envelope theorem this is the exact
+ * gradient wherever the maximiser is unique:
+ *   grad q_i = 2 g_b sum_{j in N(i)} w_ij (2 d_ij - (R_i + R_j) e_ij)           (needs w_ij == w_ji)
+ * Neither p nor w takes a gradient.  w == NULL is the weight 1 for every entry.  A rotation is stored as the
+ * unit quaternion (w, x, y, z), rotations [B, V, 4], 16-byte aligned; it is found per vertex in registers as
+ * the top eigenvector of Horn's symmetric 4 x 4 matrix by cyclic Jacobi sweeps.
+ * Limits: those of the Laplacian (NR_ERR_ARGS otherwise, and for an item stride that is neither 0 nor the
+ * item's size).
+ *
+ * The cotangent weights of the cotangent Laplacian as an output of their own, so that they can be taken from
+ * a rest shape once: w [B, nnz], w_ij = max(0, sum of c_{f,k} over the corner list of entry (i, j)), bit for
+ * bit the weights nr_cot_laplacian_forward forms on the same vertices (w_ij == w_ji bit for bit).  Limits:
+ * the cotangent Laplacian's, and B * ceil(nnz / 256) <= INT_MAX.
+ * Scratch bytes of nr_cot_weights: the half-cotangents [B][3 F]; no zero fill needed. */
+NR_API size_t nr_cot_weights_workspace_bytes(int batch_size, int num_faces);
+/* vertices [B, V, 3] -> w [B, nnz], fully written. */
+NR_API int nr_cot_weights(const float* vertices, const int32_t* faces, const int32_t* nbr_corner_offsets,
+                          const int32_t* nbr_corners, int batch_size, int num_vertices, int num_faces,
+                          int num_neighbours, float eps, float* w, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* Scratch bytes of nr_arap_forward: the per-block partial sums [B][ceil(V / 256)]; no zero fill needed. */
+NR_API size_t nr_arap_workspace_bytes(int batch_size, int num_vertices);
+/* loss [B], fully written (0 when V == 0).  rotations [B, V, 4] (what the backward reads), fully written, or
+ * NULL. */
+NR_API int nr_arap_forward(const float* vertices, const float* rest, long long rest_batch_stride, const float* w,
+                           long long w_batch_stride, const int32_t* nbr_offsets, const int32_t* nbr_index,
+                           int batch_size, int num_vertices, int num_neighbours, float* rotations, float* loss,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* grad_loss [B] -> grad_vertices [B, V, 3], fully written, from the forward's inputs and rotations. */
+NR_API int nr_arap_backward(const float* vertices, const float* rest, long long rest_batch_stride, const float* w,
+                            long long w_batch_stride, const float* rotations, const int32_t* nbr_offsets,
+                            const int32_t* nbr_index, const float* grad_loss, int batch_size, int num_vertices,
+                            int num_neighbours, float* grad_vertices, void* stream);
+
 /* Articulated meshes (skinning.py): forward kinematics of a joint tree, then linear blend skinning.  A
  * transform is 12 floats, row-major 3 x 4: [R | t].  No float atomics anywhere: every output and gradient is
  * bitwise reproducible from run to run, and an item's results do not depend on the batch it is in.

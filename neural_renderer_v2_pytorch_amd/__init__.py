@@ -17,9 +17,10 @@ from .save_obj import save_obj
 from .utils import create_textures, get_points_from_angles, imread, make_gif, to_gpu
 from .differentiation import differentiation
 from .camera import camera_transform, projection_transform
-from .mesh_loss import (CotLaplacianLoss, EdgeLengthLoss, FlattenLoss, LaplacianLoss, MeshTopology, cot_laplacian_loss,
-                        cot_laplacian_loss_torch, edge_length_loss, edge_length_loss_torch, flatten_loss, flatten_loss_torch,
-                        laplacian_loss, laplacian_loss_torch, mesh_topology)
+from .mesh_loss import (ArapLoss, CotLaplacianLoss, EdgeLengthLoss, FlattenLoss, LaplacianLoss, MeshTopology, arap_loss,
+                        arap_loss_torch, arap_rotations, arap_rotations_torch, cot_laplacian_loss, cot_laplacian_loss_torch,
+                        cot_weights, cot_weights_torch, edge_length_loss, edge_length_loss_torch, flatten_loss,
+                        flatten_loss_torch, laplacian_loss, laplacian_loss_torch, mesh_topology)
 from .image_loss import (HuberLoss, IoULoss, SquaredErrorLoss, SSIMLoss, huber_loss, huber_loss_torch, iou_loss, iou_loss_torch,
                          squared_error_loss, squared_error_loss_torch, ssim_loss, ssim_loss_torch)
 from .optimizers import Adam, adam_step_torch

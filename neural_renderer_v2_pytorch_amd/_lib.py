@@ -157,6 +157,11 @@ SIGNATURES = {
     "nr_cot_laplacian_forward": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, c_size_t,
                                          _P]),
     "nr_cot_laplacian_backward": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
+    "nr_cot_weights_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "nr_cot_weights": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, _P, c_size_t, _P]),
+    "nr_arap_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "nr_arap_forward": (c_int, [_P, _P, c_ll, _P, c_ll, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "nr_arap_backward": (c_int, [_P, _P, c_ll, _P, c_ll, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P]),
     "nr_pose_transforms_forward": (c_int, [_P, c_int, _P, c_ll, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "nr_pose_transforms_backward": (c_int, [_P, c_int, _P, c_ll, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P]),
     "nr_skin_workspace_bytes": (c_size_t, [c_int, c_int]),
@@ -211,7 +216,7 @@ def lib():
     L = ctypes.CDLL(LIB_PATH)
     # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_ssim_loss_*, nr_adam_*, nr_attributes_*,
     # point-loss entry points, the two point / mesh distance directions, nr_point_mesh_* and nr_face_point_*, and the
-    # articulated-mesh entry points, nr_pose_transforms_* and nr_skin_*):
+    # articulated-mesh entry points, nr_pose_transforms_* and nr_skin_*, nr_cot_weights and nr_arap_*):
     # a library built before them still reports the version this binding expects
     missing = [name for name in EXPORTS if not hasattr(L, name)]
     if missing:

@@ -25,7 +25,8 @@
 // per-pixel shading, XCD tile map), nr_fwd.h (setup + face-index raster), nr_shade.h (image epilogue,
 // halo cache, standalone reference kernels), nr_bwd.h (backward), nr_camera.h (look_at / look +
 // perspective), nr_projection.h (calibrated camera: K, R, t + distortion), nr_mesh_loss.h (Laplacian, cotangent
-// Laplacian, flatten and edge-length regularizers), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_ssim_loss.h (SSIM image loss), nr_adam.h
+// Laplacian, flatten and edge-length regularizers), nr_arap.h (as-rigid-as-possible energy and the cotangent weights of a
+// rest shape), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_ssim_loss.h (SSIM image loss), nr_adam.h
 // (multi-tensor Adam), nr_attributes.h (per-vertex attribute rendering), nr_point_loss.h (chamfer distance,
 // nearest points and surface sampling), nr_point_mesh.h (point-to-surface distance), nr_face_point.h (face-to-scan distance),
 // nr_skinning.h (forward kinematics and linear blend skinning), nr_host.h (workspace layouts, launch helpers, argument checks); this file holds the extern "C" ABI.
@@ -61,6 +62,7 @@
 #include "nr_camera.h"
 #include "nr_projection.h"
 #include "nr_mesh_loss.h"
+#include "nr_arap.h"
 #include "nr_image_loss.h"
 #include "nr_ssim_loss.h"
 #include "nr_adam.h"
@@ -1008,6 +1010,92 @@ int nr_cot_laplacian_backward(const float* delta, const float* w, const float* w
     nr_launch(k_cotlap_bwd, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, (hipStream_t)stream, delta, w, winv, nbr_offsets,
               nbr_index, grad_loss, V, nnz, nblk, grad_vertices);
     return check_launch("k_cotlap_bwd");
+}
+
+// ---- as-rigid-as-possible energy (nr_arap.h) ----
+size_t nr_cot_weights_workspace_bytes(int batch_size, int num_faces) {
+    if (batch_size <= 0 || num_faces <= 0 || num_faces > INT_MAX / 3) return 0;
+    return align_up((size_t)batch_size * num_faces * 3 * 4);
+}
+
+int nr_cot_weights(const float* vertices, const int32_t* faces, const int32_t* nbr_corner_offsets, const int32_t* nbr_corners,
+                   int batch_size, int num_vertices, int num_faces, int num_neighbours, float eps, float* w, void* workspace,
+                   size_t workspace_bytes, void* stream) {
+    const int B = batch_size, V = num_vertices, F = num_faces, nnz = num_neighbours;
+    int e = validate_cot_laplacian(B, V, F, nnz);
+    if (e) return e;
+    if ((long long)B * ml_blocks(nnz) > INT_MAX) return fail(NR_ERR_ARGS, "too many neighbours B=%d num_neighbours=%d", B, nnz);
+    if (!(eps >= 0.f) || !(eps < INFINITY)) return fail(NR_ERR_ARGS, "bad eps %g", (double)eps);
+    if (B == 0 || nnz == 0) return NR_OK;
+    if (V == 0 || F == 0) return fail(NR_ERR_ARGS, "neighbours without vertices or faces");
+    if (!vertices || !faces || !nbr_corner_offsets || !nbr_corners || !w) return fail(NR_ERR_ARGS, "null pointer");
+    if (!workspace || workspace_bytes < nr_cot_weights_workspace_bytes(B, F))
+        return fail(NR_ERR_WORKSPACE, "cotangent weights workspace missing or too small");
+    hipStream_t st = (hipStream_t)stream;
+    float* cot = (float*)workspace;
+    const int fblk = (int)ml_blocks(F), eblk = (int)ml_blocks(nnz);
+    nr_launch(k_cot_face, dim3((unsigned)(B * fblk)), dim3(ML_BLOCK), 0, st, vertices, faces, V, F, fblk, eps, cot);
+    e = check_launch("k_cot_face");
+    if (e) return e;
+    nr_launch(k_cot_entry, dim3((unsigned)(B * eblk)), dim3(ML_BLOCK), 0, st, nbr_corner_offsets, nbr_corners, (const float*)cot, F,
+              nnz, eblk, w);
+    return check_launch("k_cot_entry");
+}
+
+// an item stride is 0 (shared by the items) or the item's own size
+static int validate_arap(int B, int V, int nnz, long long rest_bs, const float* w, long long w_bs) {
+    if (nnz < 0) return fail(NR_ERR_ARGS, "bad size num_neighbours=%d", nnz);
+    int e = validate_mesh_loss(B, V, 0);
+    if (e) return e;
+    if (rest_bs != 0 && rest_bs != (long long)V * 3)
+        return fail(NR_ERR_ARGS, "rest_batch_stride %lld is neither 0 nor 3 V = %lld", rest_bs, (long long)V * 3);
+    if (w && w_bs != 0 && w_bs != (long long)nnz)
+        return fail(NR_ERR_ARGS, "w_batch_stride %lld is neither 0 nor num_neighbours = %d", w_bs, nnz);
+    return NR_OK;
+}
+
+size_t nr_arap_workspace_bytes(int batch_size, int num_vertices) { return nr_mesh_loss_workspace_bytes(batch_size, num_vertices); }
+
+int nr_arap_forward(const float* vertices, const float* rest, long long rest_batch_stride, const float* w, long long w_batch_stride,
+                    const int32_t* nbr_offsets, const int32_t* nbr_index, int batch_size, int num_vertices, int num_neighbours,
+                    float* rotations, float* loss, void* workspace, size_t workspace_bytes, void* stream) {
+    const int B = batch_size, V = num_vertices, nnz = num_neighbours;
+    int e = validate_arap(B, V, nnz, rest_batch_stride, w, w_batch_stride);
+    if (e) return e;
+    if (B == 0) return NR_OK;
+    if (!loss) return fail(NR_ERR_ARGS, "null loss");
+    if (V == 0 && nnz > 0) return fail(NR_ERR_ARGS, "neighbours without vertices");
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = (int)ml_blocks(V);
+    if (V > 0) {
+        if (!vertices || !rest || !nbr_offsets) return fail(NR_ERR_ARGS, "null vertices, rest or nbr_offsets");
+        if (nnz > 0 && !nbr_index) return fail(NR_ERR_ARGS, "neighbours without nbr_index");
+        if (((uintptr_t)rotations & 15) != 0) return fail(NR_ERR_ARGS, "rotations must be 16-byte aligned");
+        if (!workspace || workspace_bytes < nr_arap_workspace_bytes(B, V))
+            return fail(NR_ERR_WORKSPACE, "arap workspace missing or too small");
+        nr_launch(k_arap_fwd, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, st, vertices, rest, rest_batch_stride, w, w_batch_stride,
+                  nbr_offsets, nbr_index, V, nblk, (float4*)rotations, (float*)workspace);
+        e = check_launch("k_arap_fwd");
+        if (e) return e;
+    }
+    nr_launch(k_mesh_loss_sum, dim3((unsigned)B), dim3(ML_BLOCK), 0, st, (const float*)workspace, nblk, loss);
+    return check_launch("k_mesh_loss_sum");
+}
+
+int nr_arap_backward(const float* vertices, const float* rest, long long rest_batch_stride, const float* w, long long w_batch_stride,
+                     const float* rotations, const int32_t* nbr_offsets, const int32_t* nbr_index, const float* grad_loss,
+                     int batch_size, int num_vertices, int num_neighbours, float* grad_vertices, void* stream) {
+    const int B = batch_size, V = num_vertices, nnz = num_neighbours;
+    int e = validate_arap(B, V, nnz, rest_batch_stride, w, w_batch_stride);
+    if (e) return e;
+    if (B == 0 || V == 0) return NR_OK;
+    if (!vertices || !rest || !rotations || !nbr_offsets || !grad_loss || !grad_vertices) return fail(NR_ERR_ARGS, "null pointer");
+    if (nnz > 0 && !nbr_index) return fail(NR_ERR_ARGS, "neighbours without nbr_index");
+    if (((uintptr_t)rotations & 15) != 0) return fail(NR_ERR_ARGS, "rotations must be 16-byte aligned");
+    const int nblk = (int)ml_blocks(V);
+    nr_launch(k_arap_bwd, dim3((unsigned)(B * nblk)), dim3(ML_BLOCK), 0, (hipStream_t)stream, vertices, rest, rest_batch_stride, w,
+              w_batch_stride, (const float4*)rotations, nbr_offsets, nbr_index, grad_loss, V, nblk, grad_vertices);
+    return check_launch("k_arap_bwd");
 }
 
 // ---- articulated meshes (nr_skinning.h) ----

@@ -24,6 +24,14 @@ vertex index are ignored by both losses; duplicate faces count separately.
              else 0; loss_b = sum_i |delta_i|^2.  The clamp keeps the weighted mean a convex combination
              where both angles opposite an edge are obtuse.  The weights are constants of the backward:
              no gradient flows through them, in the fused path and in the composition alike.
+  ARAP:      for deformed vertices q against a rest shape p ([V, 3] shared by the items, or [B, V, 3]), with
+             e_ij = p_i - p_j, d_ij = q_i - q_j and entry weights w_ij == w_ji (the cotangent weights above
+             taken on p, 1, or given):  S_i = sum_{j in N(i)} w_ij e_ij d_ij^T;  R_i = the rotation (det +1)
+             maximising tr(R S_i) -- V diag(1, 1, det(V U^T)) U^T of S_i = U Sigma V^T, I where S_i = 0, any
+             maximiser where it is not unique;  loss_b = sum_i sum_{j in N(i)} w_ij |d_ij - R_i e_ij|^2.
+             The rotations are constants of the backward (they maximise: the envelope theorem makes that the
+             exact gradient): grad q_i = 2 g_b sum_{j in N(i)} w_ij (2 d_ij - (R_i + R_j) e_ij).  Neither p
+             nor the weights take a gradient (nr_arap_* / nr_cot_weights).
 
 The topology (mesh_topology) is built on the host once per faces tensor and cached, so steady-state
 calls issue no host synchronisation and a step can be captured in a HIP graph.  The fused kernels use
@@ -128,6 +136,79 @@ def cot_laplacian_loss_torch(vertices, faces, eps=1e-12, average=False):
     total = torch.zeros_like(v).index_add_(1, rows, w[:, :, None] * v.index_select(1, cols))
     delta = (v - total / torch.where(ok, W, torch.ones_like(W))[:, :, None]) * ok.to(v.dtype)[:, :, None]
     return _finish((delta * delta).sum((1, 2)), single, average)
+
+
+def _arap_prepare(vertices, rest_vertices, faces, weights):
+    """vertices as [B, V, 3], single, the topology, the rest shape as [1 or B, V, 3] (detached, the vertices'
+    device and dtype) and `weights` checked: 'cotangent', 'uniform' or a tensor as [1 or B, nnz] (detached)."""
+    v, single, topo = _prepare(vertices, faces)
+    B, V = v.shape[0], v.shape[1]
+    if not torch.is_tensor(rest_vertices) or rest_vertices.ndim not in (2, 3) or rest_vertices.shape[-1] != 3:
+        raise ValueError("rest_vertices must be a [V, 3] or [B, V, 3] tensor")
+    p = rest_vertices.detach().to(device=v.device, dtype=v.dtype)
+    p = p[None] if p.ndim == 2 else p
+    if p.shape[1] != V or p.shape[0] not in (1, B):
+        raise ValueError("rest_vertices %s do not fit vertices %s" % (list(rest_vertices.shape), list(vertices.shape)))
+    if torch.is_tensor(weights):
+        nnz = topo.nbr_index.numel()
+        w = weights.detach()
+        if not w.is_floating_point() or w.ndim not in (1, 2) or w.shape[-1] != nnz:
+            raise ValueError("weights must be a float tensor [nnz] or [B, nnz] with nnz = %d neighbour entries, got %s"
+                             % (nnz, list(weights.shape)))
+        w = w[None] if w.ndim == 1 else w
+        if w.shape[0] not in (1, B):
+            raise ValueError("weights %s do not fit vertices %s" % (list(weights.shape), list(vertices.shape)))
+        weights = w.to(device=v.device, dtype=v.dtype)
+    elif weights not in ("cotangent", "uniform"):
+        raise ValueError("weights must be 'cotangent', 'uniform' or a tensor, got %r" % (weights,))
+    return v, single, topo, p, weights
+
+
+def _arap_rotations_torch(v, p, w, topo):
+    """R [B, V, 3, 3] without gradient: per vertex the rotation maximising tr(R S), S = sum_j w e d^T, through
+    torch.linalg.svd; S = 0 gives I."""
+    with torch.no_grad():
+        rows, cols = topo.composition_index()[:2]
+        e = p.index_select(1, rows) - p.index_select(1, cols)
+        d = v.index_select(1, rows) - v.index_select(1, cols)
+        terms = (w[:, :, None] * e)[:, :, :, None] * d[:, :, None, :]
+        S = torch.zeros(v.shape[:2] + (3, 3), dtype=v.dtype, device=v.device).index_add_(1, rows, terms)
+        U, _, Vh = torch.linalg.svd(S)
+        Vm, Ut = Vh.transpose(-1, -2), U.transpose(-1, -2)
+        flip = torch.ones(v.shape[:2] + (3,), dtype=v.dtype, device=v.device)
+        flip[..., 2] = torch.linalg.det(Vm @ Ut)
+        R = (Vm * flip[..., None, :]) @ Ut
+        zero = (S == 0).all(-1).all(-1)
+        return torch.where(zero[..., None, None], torch.eye(3, dtype=v.dtype, device=v.device), R)
+
+
+def _arap_weights_torch(p, topo, weights, eps):
+    if torch.is_tensor(weights):
+        return weights
+    if weights == "uniform":
+        return torch.ones((1, topo.nbr_index.numel()), dtype=p.dtype, device=p.device)
+    return cot_weights_torch(p, topo, eps)
+
+
+def arap_rotations_torch(vertices, rest_vertices, faces, weights="cotangent", eps=1e-12):
+    """arap_rotations as torch ops (torch.linalg.svd per vertex); any device and floating dtype."""
+    v, single, topo, p, weights = _arap_prepare(vertices, rest_vertices, faces, weights)
+    R = _arap_rotations_torch(v.detach(), p, _arap_weights_torch(p, topo, weights, eps), topo)
+    return R[0] if single else R
+
+
+def arap_loss_torch(vertices, rest_vertices, faces, weights="cotangent", eps=1e-12, average=False):
+    """The ARAP energy as torch ops; any device and floating dtype.  The rotations come from
+    torch.linalg.svd under no_grad and are constants of the backward, as in the fused path; neither the rest
+    shape nor the weights take a gradient."""
+    v, single, topo, p, weights = _arap_prepare(vertices, rest_vertices, faces, weights)
+    w = _arap_weights_torch(p, topo, weights, eps)
+    R = _arap_rotations_torch(v.detach(), p, w, topo)
+    rows, cols = topo.composition_index()[:2]
+    e = p.index_select(1, rows) - p.index_select(1, cols)
+    d = v.index_select(1, rows) - v.index_select(1, cols)
+    r = d - (R.index_select(1, rows) @ e[..., None])[..., 0]
+    return _finish((w * (r * r).sum(-1)).sum(1), single, average)
 
 
 # ---- the fused path ----
@@ -293,6 +374,133 @@ class CotLaplacianFunction(torch.autograd.Function):
         return gv, None, None
 
 
+def _item_stride(t):
+    """The item stride in elements of a contiguous [1 or B, ...] tensor read per item: 0 when shared."""
+    return 0 if t.shape[0] == 1 else t[0].numel()
+
+
+class ArapFunction(torch.autograd.Function):
+    """vertices [B, V, 3], rest [1 or B, V, 3], w [1 or B, nnz] or None (uniform), float32 contiguous on the
+    GPU -> loss [B] and the rotations as unit quaternions [B, V, 4] (non-differentiable).  The backward reads
+    the inputs and the quaternions; only the vertices take a gradient.  With rotations=False and no gradient
+    needed the quaternions are not written."""
+
+    @staticmethod
+    def forward(ctx, vertices, rest, w, topo, rotations):
+        B, V, nnz = vertices.shape[0], vertices.shape[1], topo.nbr_index.numel()
+        dev = vertices.device
+        L = _lib.lib()
+        need = ctx.needs_input_grad[0]
+        loss = torch.empty(B, dtype=torch.float32, device=dev)
+        quat = torch.empty((B, V, 4), dtype=torch.float32, device=dev) if need or rotations else None
+        ws = torch.empty(L.nr_arap_workspace_bytes(B, V), dtype=torch.uint8, device=dev)
+        ctx.strides = (_item_stride(rest), 0 if w is None else _item_stride(w))
+        with _lib.on_device(dev):
+            _lib.check(L.nr_arap_forward(_lib.ptr(vertices), _lib.ptr(rest), ctx.strides[0], _lib.ptr(w), ctx.strides[1],
+                                         _lib.ptr(topo.nbr_offsets), _lib.ptr(topo.nbr_index), B, V, nnz, _lib.ptr(quat),
+                                         _lib.ptr(loss), _lib.ptr(ws), ws.numel(), _lib.stream_of(vertices)), "nr_arap_forward")
+        ctx.topo, ctx.uniform = topo, w is None
+        if need:
+            ctx.save_for_backward(vertices, rest, quat, *(() if w is None else (w,)))
+        if quat is None:
+            quat = loss.new_empty(0)
+        ctx.mark_non_differentiable(quat)
+        return loss, quat
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_loss, _grad_quat):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        vertices, rest, quat = ctx.saved_tensors[:3]
+        w = None if ctx.uniform else ctx.saved_tensors[3]
+        topo = ctx.topo
+        g = grad_loss.to(torch.float32).contiguous()
+        gv = torch.empty_like(vertices)
+        with _lib.on_device(vertices.device):
+            _lib.check(_lib.lib().nr_arap_backward(_lib.ptr(vertices), _lib.ptr(rest), ctx.strides[0], _lib.ptr(w), ctx.strides[1],
+                                                   _lib.ptr(quat), _lib.ptr(topo.nbr_offsets), _lib.ptr(topo.nbr_index),
+                                                   _lib.ptr(g), vertices.shape[0], vertices.shape[1], topo.nbr_index.numel(),
+                                                   _lib.ptr(gv), _lib.stream_of(vertices)), "nr_arap_backward")
+        return gv, None, None, None, None
+
+
+def _cot_weights_fused(v, topo, eps):
+    """w [B, nnz] of float32 contiguous GPU vertices [B, V, 3]: nr_cot_weights."""
+    B, V, F, nnz = v.shape[0], v.shape[1], topo.faces.shape[0] if topo.faces is not None else 0, topo.nbr_index.numel()
+    w = torch.empty((B, nnz), dtype=torch.float32, device=v.device)
+    if nnz == 0:
+        return w
+    corner_offsets, corners = topo.corner_csr()
+    L = _lib.lib()
+    ws = torch.empty(L.nr_cot_weights_workspace_bytes(B, F), dtype=torch.uint8, device=v.device)
+    with _lib.on_device(v.device):
+        _lib.check(L.nr_cot_weights(_lib.ptr(v), _lib.ptr(topo.faces), _lib.ptr(corner_offsets), _lib.ptr(corners), B, V, F, nnz,
+                                    eps, _lib.ptr(w), _lib.ptr(ws), ws.numel(), _lib.stream_of(v)), "nr_cot_weights")
+    return w
+
+
+def cot_weights(vertices, faces, eps=1e-12):
+    """The clamped cotangent weight w_ij = max(0, sum of the half-cotangents opposite edge {i, j}) of every
+    entry of the neighbour CSR, [B, nnz] for vertices [B, V, 3] ([nnz] for [V, 3]), without gradient: the
+    weights cot_laplacian_loss forms, bit for bit on the fused path, and w_ij == w_ji bit for bit.  float32 GPU
+    vertices run the fused kernels; everything else cot_weights_torch.  `faces` is [F, 3] or a MeshTopology
+    that knows its faces; the entries are in the order of its nbr_index."""
+    v, single, topo = _prepare(vertices, faces)
+    v = v.detach()
+    w = _cot_weights_fused(v.contiguous(), topo, float(eps)) if _fused(v) else cot_weights_torch(v, topo, eps)
+    return w[0] if single else w
+
+
+def _arap_fused(v, p, weights, topo, eps, rotations):
+    """(loss [B], quaternions [B, V, 4] or an empty tensor) of ArapFunction for checked inputs."""
+    p = p.contiguous()
+    if torch.is_tensor(weights):
+        w = weights.contiguous()
+    else:
+        w = None if weights == "uniform" else _cot_weights_fused(p, topo, float(eps))
+    return ArapFunction.apply(v.contiguous(), p, w, topo, rotations)
+
+
+def arap_loss(vertices, rest_vertices, faces, weights="cotangent", eps=1e-12, average=False):
+    """The as-rigid-as-possible energy of the deformed `vertices` against the rest shape `rest_vertices`
+    ([V, 3], shared by the items, or [B, V, 3]): with e_ij = p_i - p_j and d_ij = q_i - q_j over the
+    neighbour entries of `faces`,
+        S_i = sum_j w_ij e_ij d_ij^T,  R_i = the rotation (det +1) maximising tr(R S_i)  (I where S_i = 0),
+        loss_b = sum_i sum_{j in N(i)} w_ij |d_ij - R_i e_ij|^2.
+    `weights`: 'cotangent' (cot_laplacian_loss's clamped weights, computed on the rest shape with `eps`),
+    'uniform' (1), or a float tensor [nnz] or [B, nnz] in the order of MeshTopology.nbr_index, used as given:
+    the caller guarantees w_ij == w_ji.  The rotations are constants of the backward -- they maximise, so the
+    gradient is exact wherever the maximiser is unique -- and neither the rest shape nor the weights take a
+    gradient: the gradient reaches `vertices` only.  Shapes, dispatch, `average` and batch-expanded
+    vertices as laplacian_loss; float32 GPU vertices run the fused kernels, everything else arap_loss_torch.
+    ArapLoss computes the weights of a fixed rest shape once."""
+    if not _fused(vertices):
+        return arap_loss_torch(vertices, rest_vertices, faces, weights, eps, average)
+    v, single, topo, p, weights = _arap_prepare(vertices, rest_vertices, faces, weights)
+    return _finish(_arap_fused(v, p, weights, topo, eps, False)[0], single, average)
+
+
+def _quaternion_matrices(q):
+    """Rotation matrices [..., 3, 3] of unit quaternions [..., 4] (w, x, y, z)."""
+    w, x, y, z = q.unbind(-1)
+    rows = [1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+            2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+            2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]
+    return torch.stack(rows, -1).reshape(q.shape[:-1] + (3, 3))
+
+
+def arap_rotations(vertices, rest_vertices, faces, weights="cotangent", eps=1e-12):
+    """The best-fitting rotation R_i of every vertex neighbourhood of arap_loss, [B, V, 3, 3] ([V, 3, 3] for
+    [V, 3] vertices), without gradient: R_i e_ij is the rest edge as the deformed mesh holds it.  Arguments
+    and dispatch as arap_loss."""
+    if not _fused(vertices):
+        return arap_rotations_torch(vertices, rest_vertices, faces, weights, eps)
+    v, single, topo, p, weights = _arap_prepare(vertices, rest_vertices, faces, weights)
+    R = _quaternion_matrices(_arap_fused(v.detach(), p, weights, topo, eps, True)[1])
+    return R[0] if single else R
+
+
 def laplacian_loss(vertices, faces, average=False):
     """sum_i |v_i - mean of i's neighbours|^2 per item: [B] for vertices [B, V, 3], a 0-dim tensor for
     [V, 3] or with average=True (the mean over the items).  `faces` is [F, 3] (shared by the items) or a
@@ -388,3 +596,36 @@ class CotLaplacianLoss(torch.nn.Module):
 
     def forward(self, vertices):
         return cot_laplacian_loss(vertices, self.topology, self.eps, self.average)
+
+
+class ArapLoss(torch.nn.Module):
+    """arap_loss against a fixed rest shape: the module holds the topology of `faces`, keeps `rest_vertices`
+    ([V, 3] or [B, V, 3]) as a buffer, and forms the weights ('cotangent' with `eps`, 'uniform' or a tensor,
+    as arap_loss) once per device and dtype of the vertices it is called with, at the first such call."""
+
+    def __init__(self, rest_vertices, faces, weights="cotangent", average=False, eps=1e-12):
+        super().__init__()
+        if not torch.is_tensor(rest_vertices) or rest_vertices.ndim not in (2, 3) or rest_vertices.shape[-1] != 3:
+            raise ValueError("rest_vertices must be a [V, 3] or [B, V, 3] tensor")
+        self.topology = mesh_topology(faces, rest_vertices.shape[-2])
+        self.register_buffer("rest_vertices", rest_vertices.detach().clone())
+        self.weights, self.eps, self.average = weights, eps, average
+        self._held = {}  # (device, dtype) -> (the buffer's version, rest shape, weights) as arap_loss takes them
+
+    def held(self, vertices):
+        """The rest shape and the weights on the device and in the dtype of `vertices`."""
+        key = (vertices.device, vertices.dtype)
+        hit = self._held.get(key)
+        if hit is None or hit[0] != (self.rest_vertices.data_ptr(), self.rest_vertices._version):
+            p = self.rest_vertices.to(device=key[0], dtype=key[1])
+            w = self.weights
+            if torch.is_tensor(w):
+                w = w.detach().to(device=key[0], dtype=key[1])
+            elif w == "cotangent":
+                w = cot_weights(p, self.topology, self.eps)
+            hit = self._held[key] = ((self.rest_vertices.data_ptr(), self.rest_vertices._version), p, w)
+        return hit[1], hit[2]
+
+    def forward(self, vertices):
+        p, w = self.held(vertices)
+        return arap_loss(vertices, p, self.topology, w, self.eps, self.average)

@@ -94,6 +94,21 @@ def rigged_tube(rings=16, segments=12, joints=4, radius=0.2, height=1.2):
     return (v.astype(np.float32), f, c_j.astype(np.float32), parents, weights.astype(np.float32), indices)
 
 
+def bent(vertices, angle=1.0):
+    """`vertices` [V, 3] bent in the x-y plane about the z axis: the y axis becomes an arc that turns by
+    `angle` rad over the mesh's height, the arc length kept, cross-sections staying rigid (float64 in, the
+    input's dtype out).  A non-rigid deformation that is locally a rotation: what an ARAP term leaves alone."""
+    v = np.asarray(vertices, np.float64)
+    lo, hi = v[:, 1].min(), v[:, 1].max()
+    if not angle or hi <= lo:
+        return np.asarray(vertices).copy()
+    k = angle / (hi - lo)  # curvature; the centre of the arc is at x = 1 / k
+    t = k * (v[:, 1] - lo)
+    r = 1. / k - v[:, 0]
+    out = np.stack([1. / k - r * np.cos(t), lo + r * np.sin(t), v[:, 2]], -1)
+    return out.astype(np.asarray(vertices).dtype)
+
+
 def subdivide(v, f, vt=None, ft=None):
     """Midpoint subdivision: every triangle into 4 (shared edge midpoints, computed in float64);
     the same on the uv mesh when given.  SURVEY.md section 8d: the car 4e49873... (F=3644) once
