@@ -833,6 +833,76 @@ NR_API int nr_face_point_backward(const float* points, long long points_batch_st
                                   int batch_size, int num_points, int num_vertices, int num_faces,
                                   float* grad_points, float* grad_vertices, void* stream);
 
+/* Rigid registration (rigid.py; no reference counterpart): the closed-form weighted similarity between
+ * corresponding points, and point-to-point ICP built on it.
+ *
+ * rigid_align: x [B, N, 3] contiguous, y [B, N, 3] at the item stride y_batch_stride in elements (0: one
+ * [N, 3] set shared by every item), weights w [B, N] at the item stride w_batch_stride (0: shared), non-negative
+ * and used as given, or NULL: the weight 1.  Minimises sum_i w_i |s R x_i + t - y_i|^2 over proper rotations R
+ * (det +1, never a reflection), t, and s when `scale` is set (else s = 1):
+ *   W    = sum w,   xbar = sum w x / W,   ybar = sum w y / W
+ *   A    = sum w (y - ybar) (x - xbar)^T                 (3 x 3, row-major)
+ *   var  = sum w |x - xbar|^2
+ *   R    = argmax tr(R^T A)                              (Horn's quaternion method, nr_arap.h's Jacobi sweeps)
+ *   s    = tr(R^T A) / var   with scale,  1 without
+ *   t    = ybar - s R xbar
+ *   condition = (s2 + d s3) / s1 of A's singular values s1 >= s2 >= s3, d = sign det A: (l1 - l2) / (l1 + l2) of
+ *          the two largest eigenvalues of Horn's 4 x 4 matrix.  Near 0 the rotation is not determined.
+ * Corner cases, all finite: W == 0 gives R = I, t = 0, s = 1, condition = 0;  A == 0 (N = 1, coincident points)
+ * gives R = I and condition = 0;  var == 0 gives s = 1;  where the maximiser is not unique (collinear points,
+ * N = 2) any maximiser is returned, orthonormal with det +1.
+ * The sums are never raw second moments: the centroids are summed relative to the item's first pair, and A and
+ * var from centred points, so a cloud far from the origin loses nothing.
+ * Backward, from the gradients gR [B, 9], gt [B, 3], gs [B] of the outputs (any may be NULL: zero), closed form:
+ *   through t:  g_ybar = gt,  g_xbar = -s R^T gt,  G = gR - s gt xbar^T,  g_s = gs - gt . (R xbar)
+ *   through s:  g_tau = g_s / var,  g_var = -g_s s / var            (scale set and var > 0; else both 0)
+ *   through R:  P = R^T A (symmetric), K = tr(P) I - P, a perturbation dA turns R by dR = R [omega]x with
+ *               K omega = axial(R^T dA - dA^T R); so with m = axial(R^T G - G^T R) and u = K^{-1} m (adjugate),
+ *               gA = g_tau R + R [u]x.  K's smallest eigenvalue is s2 + d s3: where condition <=
+ *               NR_RIGID_MIN_CONDITION the rotation passes no gradient (u = 0).
+ *   grad x_n = w_n (gA^T (y_n - ybar) + 2 g_var (x_n - xbar) + g_xbar / W)
+ *   grad y_n = w_n (gA (x_n - xbar) + g_ybar / W)                   (the centring terms cancel)
+ * The weights take no gradient.  No float atomics, every sum in one fixed order: all outputs and gradients are
+ * bitwise reproducible, and an item's results do not depend on its batch.
+ *
+ * icp: x [B, N, 3] onto y [B, M, 3] (item stride y_batch_stride, 0: shared), exactly `iterations` updates, no
+ * early exit and nothing read back by the host.  `transform` [B, 13] = (R [9] row-major, t [3], s) per item is
+ * the start on entry and the result on return.  Pass k = 0 .. iterations - 1: index_i = the nearest y of
+ * s R x_i + t (fma(dz, dz, fma(dy, dy, dx dx)), the lowest index among exact ties), dist2_i its squared distance;
+ * w_i = 1, or 0 where dist2_i > max_distance^2 (max_distance < 0: no rejection); then (R, t, s) =
+ * rigid_align(x, y[index], w) of the original x -- left as it was when no pair is kept.  A last pass writes index
+ * and dist2 under the returned transform.  rmse [B, iterations + 1]: entry k = sqrt(sum w dist2 / sum w) of pass k,
+ * 0 when no pair is kept.
+ *
+ * Checked before any launch (NR_ERR_ARGS; NR_ERR_WORKSPACE for a missing or short workspace): N, M >= 1,
+ * iterations >= 0, B <= 65535, B * max(N, M) <= INT_MAX - 4096, item strides 0 or the item's size, non-null
+ * pointers.  With B == 0 nothing is launched. */
+#define NR_RIGID_MIN_CONDITION 1e-6f
+enum { NR_RIGID_RECORD_FLOATS = 32, NR_RIGID_TRANSFORM_FLOATS = 13 };
+/* Scratch bytes of nr_rigid_align_forward and _backward (the per-chunk partial sums of 1024 points; the backward
+ * uses the first 64 B bytes); no zero fill needed; 0 when a size is not positive. */
+NR_API size_t nr_rigid_workspace_bytes(int batch_size, int num_points);
+/* R [B, 9], t [B, 3], s [B], condition [B], record [B, NR_RIGID_RECORD_FLOATS] (what the backward reads), all
+ * fully written; condition and record may be NULL. */
+NR_API int nr_rigid_align_forward(const float* x, const float* y, long long y_batch_stride, const float* w,
+                                  long long w_batch_stride, int batch_size, int num_points, int scale, float* R,
+                                  float* t, float* s, float* condition, float* record, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+/* grad_x [B, N, 3], grad_y [B, N, 3] (dense, also for a shared y); either may be NULL, each one given is fully
+ * written.  x, y, w and scale are the forward's. */
+NR_API int nr_rigid_align_backward(const float* x, const float* y, long long y_batch_stride, const float* w,
+                                   long long w_batch_stride, const float* record, const float* grad_R,
+                                   const float* grad_t, const float* grad_s, int batch_size, int num_points, int scale,
+                                   float* grad_x, float* grad_y, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+/* Scratch bytes of nr_icp (the partial sums, and where the targets are split over several blocks their partial
+ * (d2, j) pairs); no zero fill needed; 0 when a size is not positive. */
+NR_API size_t nr_icp_workspace_bytes(int batch_size, int num_x, int num_y);
+/* transform [B, 13] in and out; rmse [B, iterations + 1], index [B, N], dist2 [B, N] fully written. */
+NR_API int nr_icp(const float* x, const float* y, long long y_batch_stride, int batch_size, int num_x, int num_y,
+                  int iterations, int scale, float max_distance, float* transform, float* rmse, int32_t* index,
+                  float* dist2, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Diagnostics (no reference counterpart): the kernels replace some IEEE divisions by a shortened
  * form of the compiler's own division sequence inside a guarded operand range (DESIGN.md,
  * "Numerics").  This runs both forms on n operand pairs so tests can check they agree bit for bit. */
@@ -850,7 +920,7 @@ NR_API int nr_profile_enable(int on);
 NR_API int nr_profile_read(const char* kernel, float* ms);
 
 /* Launch record (no reference counterpart; the tests use it to assert which kernel variant ran).
- * For the most recent launch of `kernel` ("k_raster_fwd", "k_raster_bwd", or "k_chamfer_nn" / "k_point_face_nn" / "k_face_point_nn": 256 threads) in this process
+ * For the most recent launch of `kernel` ("k_raster_fwd", "k_raster_bwd", or "k_chamfer_nn" / "k_point_face_nn" / "k_face_point_nn" / "k_icp_nn": 256 threads) in this process
  * (process-wide, like the profiling hook; torch issues a backward from its autograd thread): block_threads = threads per block (k_raster_fwd: 256 = four 16x16 quadrants per
  * 32x32 bin, 1024 = one wave per 8x8 block; k_raster_bwd: 256 = 2 pixels per lane, 512 = 1 pixel
  * per lane) and flags = NR_LAUNCH_* bits.  NR_ERR_ARGS when none was recorded. */
@@ -867,7 +937,9 @@ enum { NR_LAUNCH_FUSED_SHADE = 1, NR_LAUNCH_STATIC_CHANNELS = 2, NR_LAUNCH_TWO_P
        /* k_point_face_nn: the faces were split over several blocks and combined */
        NR_LAUNCH_SPLIT_FACES = 8192,
        /* k_face_point_nn: the points were split over several blocks and combined */
-       NR_LAUNCH_SPLIT_POINTS = 16384 };
+       NR_LAUNCH_SPLIT_POINTS = 16384,
+       /* k_icp_nn: the targets were split over several blocks and combined */
+       NR_LAUNCH_SPLIT_TARGETS = 32768 };
 NR_API int nr_last_launch(const char* kernel, int* block_threads, int* flags);
 
 /* Dispatch order of a raster launch's tiles (no reference counterpart; host only, for tests and the

@@ -34,5 +34,6 @@ from .point_loss import (ChamferLoss, MeshPointLoss, PointMeshLoss, chamfer_dist
 from .skinning import (NR_RODRIGUES_SERIES, NR_SKIN_CHUNK, NR_SKIN_MAX_INFLUENCES, NR_SKIN_MAX_JOINTS, Skeleton, SkinBinding,
                        Skinning, pose_transforms, pose_transforms_torch, rodrigues_torch, skeleton, skin_binding,
                        skin_vertices, skin_vertices_torch)
+from .rigid import NR_RIGID_MIN_CONDITION, ICPResult, icp, icp_torch, rigid_align, rigid_align_torch
 
 __version__ = '2.0.2+mi355x.1'

@@ -25,6 +25,7 @@ NR_LAUNCH_LIGHTS, NR_LAUNCH_BACKGROUNDS, NR_LAUNCH_SIL_ONLY = 256, 512, 1024  # 
 NR_LAUNCH_SPLIT_X_TO_Y, NR_LAUNCH_SPLIT_Y_TO_X = 2048, 4096  # k_chamfer_nn: a direction's targets split over several blocks
 NR_LAUNCH_SPLIT_FACES = 8192  # k_point_face_nn: the faces split over several blocks
 NR_LAUNCH_SPLIT_POINTS = 16384  # k_face_point_nn: the points split over several blocks
+NR_LAUNCH_SPLIT_TARGETS = 32768  # k_icp_nn: the targets split over several blocks
 NR_HOT_MAX, NR_HOT_COPIES = 256, 32
 
 c_int, c_float, c_void_p, c_size_t, c_ll = ctypes.c_int, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_longlong
@@ -65,6 +66,9 @@ NR_POINT_MESH_SPLIT_BLOCKS = 4096  # PM_SPLIT_BLOCKS: the faces are split over f
 NR_FACE_POINT_TILE, NR_FACE_POINT_FBLOCK = 64, 256  # csrc/nr_face_point.h FP_TILE (points in LDS), FP_FBLOCK (faces per block)
 NR_FACE_POINT_SPLIT_BLOCKS = 4096  # FP_SPLIT_BLOCKS: the points are split over further blocks while a launch has fewer
 NR_COT_MIN_WEIGHT = 1e-6  # include/nr_raster.h: a vertex whose cotangent weights sum to no more has delta = 0
+# include/nr_raster.h: at or below this condition rigid_align's rotation passes no gradient; floats of its saved
+# per-item record and of a transform (R, t, s) in device memory; csrc/nr_rigid.h RG_CHUNK: points per block of its sums
+NR_RIGID_MIN_CONDITION, NR_RIGID_RECORD_FLOATS, NR_RIGID_TRANSFORM_FLOATS, NR_RIGID_CHUNK = 1e-6, 32, 13, 1024
 # include/nr_raster.h: joints of a skeleton, influences per vertex, entries of a joint's CSR row per block of
 # k_skin_bwd_transforms, and the |r|^2 below which Rodrigues' coefficients come from their series
 NR_SKIN_MAX_JOINTS, NR_SKIN_MAX_INFLUENCES, NR_SKIN_CHUNK, NR_RODRIGUES_SERIES = 256, 8, 256, 1e-4
@@ -196,6 +200,11 @@ SIGNATURES = {
     "nr_face_point_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "nr_face_point_forward": (c_int, [_P, c_ll, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
     "nr_face_point_backward": (c_int, [_P, c_ll, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "nr_rigid_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "nr_rigid_align_forward": (c_int, [_P, _P, c_ll, _P, c_ll, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "nr_rigid_align_backward": (c_int, [_P, _P, c_ll, _P, c_ll, _P, _P, _P, _P, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "nr_icp_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "nr_icp": (c_int, [_P, _P, c_ll, c_int, c_int, c_int, c_int, c_int, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -216,7 +225,7 @@ def lib():
     L = ctypes.CDLL(LIB_PATH)
     # additions within one ABI version (the nr_projection_*, mesh-loss, image-loss, nr_ssim_loss_*, nr_adam_*, nr_attributes_*,
     # point-loss entry points, the two point / mesh distance directions, nr_point_mesh_* and nr_face_point_*, and the
-    # articulated-mesh entry points, nr_pose_transforms_* and nr_skin_*, nr_cot_weights and nr_arap_*):
+    # articulated-mesh entry points, nr_pose_transforms_* and nr_skin_*, nr_cot_weights and nr_arap_*, nr_rigid_* and nr_icp):
     # a library built before them still reports the version this binding expects
     missing = [name for name in EXPORTS if not hasattr(L, name)]
     if missing:
@@ -242,7 +251,7 @@ def lib():
 def last_launch(kernel):
     """(threads per block, NR_LAUNCH_* flags) of the latest launch of `kernel` in this process: the variant the
     library actually ran.  kernel: "k_raster_fwd", "k_raster_bwd", "k_chamfer_nn", or the nearest-neighbour loop of a
-    point / mesh distance direction, "k_point_face_nn" or "k_face_point_nn"."""
+    point / mesh distance direction, "k_point_face_nn" or "k_face_point_nn", or the ICP's, "k_icp_nn"."""
     t, f = c_int(), c_int()
     check(lib().nr_last_launch(kernel.encode(), ctypes.byref(t), ctypes.byref(f)), "nr_last_launch")
     return t.value, f.value

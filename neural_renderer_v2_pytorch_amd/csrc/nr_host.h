@@ -170,6 +170,36 @@ ChamferLayout chamfer_layout(int B, int nq, int nt) {
     return {p, c.take((size_t)B * nq * 4), c.take_if(p.nsplit > 1, part), c.take_if(p.nsplit > 1, part), c.off};
 }
 
+// rigid_align (nr_rigid.h): pass (a)'s partial sums [B][chunks][RG_SUMS], then pass (b)'s [B][chunks][RG_MOM], a chunk
+// being RG_CHUNK points.  The backward keeps its per-item gradients [B][RG_GRAD] at the start of the same buffer
+// (never larger: a chunk's two partials are RG_SUMS + RG_MOM >= RG_GRAD floats).
+struct RigidLayout {
+    int nchunk;
+    size_t sums, moments, total;
+};
+RigidLayout rigid_layout(int B, int N) {
+    const int nchunk = (int)(((long long)N + RG_CHUNK - 1) / RG_CHUNK);
+    Cutter c;
+    return {nchunk, c.take((size_t)B * nchunk * RG_SUMS * 4), c.take((size_t)B * nchunk * RG_MOM * 4), c.off};
+}
+static_assert(RG_SUMS + RG_MOM >= RG_GRAD, "the backward's gradients fit the forward's workspace");
+
+// icp: rigid_align's two pieces for the N queries, then on the split path of k_icp_nn the partial d2 and j
+// [B, nsplit, N] each
+struct IcpLayout {
+    SplitPlan plan;
+    RigidLayout rigid;
+    size_t part_d2, part_j, total;
+};
+IcpLayout icp_layout(int B, int N, int M) {
+    const SplitPlan p = split_plan(B, N, M, PL_QBLOCK, PL_TILE, PL_SPLIT_BLOCKS);
+    const RigidLayout r = rigid_layout(B, N);
+    const size_t part = (size_t)B * p.nsplit * N * 4;
+    Cutter c;
+    c.off = r.total;
+    return {p, r, c.take_if(p.nsplit > 1, part), c.take_if(p.nsplit > 1, part), c.off};
+}
+
 // The two directions of the point / mesh distance, which share one host path (nr_raster.hip): point -> face (for
 // every point its nearest face, nr_point_mesh.h) and face -> point (for every face its nearest point,
 // nr_face_point.h).  Everything that tells them apart on the host is stated here.

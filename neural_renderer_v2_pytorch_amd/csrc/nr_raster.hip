@@ -29,7 +29,7 @@
 // rest shape), nr_image_loss.h (squared-error, Huber and IoU image losses), nr_ssim_loss.h (SSIM image loss), nr_adam.h
 // (multi-tensor Adam), nr_attributes.h (per-vertex attribute rendering), nr_point_loss.h (chamfer distance,
 // nearest points and surface sampling), nr_point_mesh.h (point-to-surface distance), nr_face_point.h (face-to-scan distance),
-// nr_skinning.h (forward kinematics and linear blend skinning), nr_host.h (workspace layouts, launch helpers, argument checks); this file holds the extern "C" ABI.
+// nr_skinning.h (forward kinematics and linear blend skinning), nr_rigid.h (rigid alignment and ICP), nr_host.h (workspace layouts, launch helpers, argument checks); this file holds the extern "C" ABI.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -71,6 +71,7 @@
 #include "nr_point_mesh.h"
 #include "nr_face_point.h"
 #include "nr_skinning.h"
+#include "nr_rigid.h"
 #include "nr_host.h"
 
 
@@ -1389,6 +1390,132 @@ int nr_sample_points_backward(const int32_t* faces, const int32_t* face, const f
     return check_launch("k_sample_points_bwd");
 }
 
+// ---- rigid registration (nr_rigid.h) ----
+static int validate_rigid(int B, int N, int M, long long y_bs, const float* w, long long w_bs) {
+    if (B < 0) return fail(NR_ERR_ARGS, "bad batch size B=%d", B);
+    if (N <= 0 || M <= 0) return fail(NR_ERR_ARGS, "empty point set N=%d M=%d (both must be at least 1)", N, M);
+    if (B > 65535) return fail(NR_ERR_ARGS, "too many items B=%d (at most 65535)", B);
+    if ((long long)B * (N > M ? N : M) > INT_MAX - 4096) return fail(NR_ERR_ARGS, "too many points B=%d N=%d M=%d", B, N, M);
+    if (y_bs != 0 && y_bs != (long long)M * 3)
+        return fail(NR_ERR_ARGS, "y_batch_stride %lld is neither 0 nor 3 * %d", y_bs, M);
+    if (w && w_bs != 0 && w_bs != (long long)N) return fail(NR_ERR_ARGS, "w_batch_stride %lld is neither 0 nor N = %d", w_bs, N);
+    return NR_OK;
+}
+
+size_t nr_rigid_workspace_bytes(int batch_size, int num_points) {
+    if (batch_size <= 0 || num_points <= 0) return 0;
+    return rigid_layout(batch_size, num_points).total;
+}
+
+// Passes (a), (b) and (c) of nr_rigid.h on the pairs p: the solve of rigid_align and of one ICP update.
+static int rigid_solve(const RgPairs& p, int B, const RigidLayout& wl, char* ws, int scale, int keep, const RgOut& out, hipStream_t st) {
+    float* part_a = (float*)(ws + wl.sums);
+    float* part_b = (float*)(ws + wl.moments);
+    const dim3 grid((unsigned)wl.nchunk, (unsigned)B);
+    nr_launch(k_rigid_sums, grid, dim3(RG_BLOCK), 0, st, p, wl.nchunk, part_a);
+    int e = check_launch("k_rigid_sums");
+    if (e) return e;
+    nr_launch(k_rigid_moments, grid, dim3(RG_BLOCK), 0, st, p, wl.nchunk, (const float*)part_a, part_b);
+    e = check_launch("k_rigid_moments");
+    if (e) return e;
+    nr_launch(k_rigid_solve, dim3((unsigned)B), dim3(RG_BLOCK), 0, st, p, wl.nchunk, (const float*)part_a, (const float*)part_b, scale,
+              keep, 0, out);
+    return check_launch("k_rigid_solve");
+}
+
+int nr_rigid_align_forward(const float* x, const float* y, long long y_batch_stride, const float* w, long long w_batch_stride,
+                           int batch_size, int num_points, int scale, float* R, float* t, float* s, float* condition, float* record,
+                           void* workspace, size_t workspace_bytes, void* stream) {
+    const int B = batch_size, N = num_points;
+    int e = validate_rigid(B, N, N, y_batch_stride, w, w_batch_stride);
+    if (e) return e;
+    if (B == 0) return NR_OK;
+    if (!x || !y || !R || !t || !s) return fail(NR_ERR_ARGS, "null x, y, R, t or s");
+    const RigidLayout wl = rigid_layout(B, N);
+    if (!workspace || workspace_bytes < wl.total) return fail(NR_ERR_WORKSPACE, "rigid_align workspace missing or too small");
+    RgPairs p = {};
+    p.x = x, p.y = y, p.w = w, p.y_stride = y_batch_stride, p.w_stride = w_batch_stride, p.max_d2 = INFINITY, p.N = N;
+    RgOut out = {};
+    out.R = R, out.t = t, out.s = s, out.condition = condition, out.record = record;
+    return rigid_solve(p, B, wl, (char*)workspace, scale != 0, 0, out, (hipStream_t)stream);
+}
+
+int nr_rigid_align_backward(const float* x, const float* y, long long y_batch_stride, const float* w, long long w_batch_stride,
+                            const float* record, const float* grad_R, const float* grad_t, const float* grad_s, int batch_size,
+                            int num_points, int scale, float* grad_x, float* grad_y, void* workspace, size_t workspace_bytes,
+                            void* stream) {
+    const int B = batch_size, N = num_points;
+    int e = validate_rigid(B, N, N, y_batch_stride, w, w_batch_stride);
+    if (e) return e;
+    if (B == 0 || (!grad_x && !grad_y)) return NR_OK;
+    if (!x || !y || !record) return fail(NR_ERR_ARGS, "null x, y or record");
+    if (!workspace || workspace_bytes < rigid_layout(B, N).total)
+        return fail(NR_ERR_WORKSPACE, "rigid_align workspace missing or too small");
+    hipStream_t st = (hipStream_t)stream;
+    float* gitem = (float*)workspace;
+    nr_launch(k_rigid_bwd_item, grid_1d(B, RG_BLOCK), dim3(RG_BLOCK), 0, st, record, grad_R, grad_t, grad_s, B, scale != 0, gitem);
+    e = check_launch("k_rigid_bwd_item");
+    if (e) return e;
+    RgPairs p = {};
+    p.x = x, p.y = y, p.w = w, p.y_stride = y_batch_stride, p.w_stride = w_batch_stride, p.max_d2 = INFINITY, p.N = N;
+    nr_launch(k_rigid_bwd_points, grid_1d(N, RG_BLOCK, B), dim3(RG_BLOCK), 0, st, p, record, (const float*)gitem, grad_x, grad_y);
+    return check_launch("k_rigid_bwd_points");
+}
+
+size_t nr_icp_workspace_bytes(int batch_size, int num_x, int num_y) {
+    if (batch_size <= 0 || num_x <= 0 || num_y <= 0) return 0;
+    return icp_layout(batch_size, num_x, num_y).total;
+}
+
+int nr_icp(const float* x, const float* y, long long y_batch_stride, int batch_size, int num_x, int num_y, int iterations, int scale,
+           float max_distance, float* transform, float* rmse, int32_t* index, float* dist2, void* workspace, size_t workspace_bytes,
+           void* stream) {
+    const int B = batch_size, N = num_x, M = num_y;
+    int e = validate_rigid(B, N, M, y_batch_stride, nullptr, 0);
+    if (e) return e;
+    if (iterations < 0) return fail(NR_ERR_ARGS, "negative iterations %d", iterations);
+    if (max_distance != max_distance) return fail(NR_ERR_ARGS, "max_distance is NaN");
+    if (B == 0) return NR_OK;
+    if (!x || !y || !transform || !rmse || !index || !dist2) return fail(NR_ERR_ARGS, "null pointer");
+    const IcpLayout wl = icp_layout(B, N, M);
+    if (!workspace || workspace_bytes < wl.total) return fail(NR_ERR_WORKSPACE, "icp workspace missing or too small");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    const SplitPlan plan = wl.plan;
+    IcpDir d = {};
+    d.x = x, d.y = y, d.transform = transform, d.y_stride = y_batch_stride, d.nq = N, d.nt = M, d.nsplit = plan.nsplit;
+    d.dist2 = plan.nsplit > 1 ? (float*)(ws + wl.part_d2) : dist2;
+    d.index = plan.nsplit > 1 ? (int32_t*)(ws + wl.part_j) : index;
+    RgPairs p = {};
+    p.x = x, p.y = y, p.index = index, p.dist2 = dist2, p.y_stride = y_batch_stride, p.N = N;
+    p.max_d2 = max_distance < 0.f ? INFINITY : max_distance * max_distance;
+    for (int k = 0; k <= iterations; k++) {
+        nr_launch(k_icp_nn, dim3((unsigned)(plan.nqb * plan.nsplit), (unsigned)B), dim3(PL_BLOCK), 0, st, d);
+        g_last_icp.store(LaunchRec{PL_BLOCK, plan.nsplit > 1 ? NR_LAUNCH_SPLIT_TARGETS : 0});
+        e = check_launch("k_icp_nn");
+        if (e) return e;
+        e = combine_split(d.dist2, d.index, B, N, plan.nsplit, dist2, index, st);
+        if (e) return e;
+        RgOut out = {};
+        out.rmse = rmse + k, out.rmse_stride = iterations + 1;
+        if (k < iterations) {
+            out.transform = transform;
+            e = rigid_solve(p, B, wl.rigid, ws, scale != 0, 1, out, st);
+            if (e) return e;
+        } else {  // the evaluation pass: rmse alone
+            float* part_a = (float*)(ws + wl.rigid.sums);
+            nr_launch(k_rigid_sums, dim3((unsigned)wl.rigid.nchunk, (unsigned)B), dim3(RG_BLOCK), 0, st, p, wl.rigid.nchunk, part_a);
+            e = check_launch("k_rigid_sums");
+            if (e) return e;
+            nr_launch(k_rigid_solve, dim3((unsigned)B), dim3(RG_BLOCK), 0, st, p, wl.rigid.nchunk, (const float*)part_a,
+                      (const float*)nullptr, 0, 1, 1, out);
+            e = check_launch("k_rigid_solve");
+            if (e) return e;
+        }
+    }
+    return NR_OK;
+}
+
 // ---- point-to-surface and face-to-scan distance (nr_point_mesh.h, nr_face_point.h): one path, a PairDir each ----
 // What every forward and backward of a direction starts with: the sizes and the stride; then, with nothing to
 // do (B == 0, or nothing wanted), NR_OK and *go false: no pointer is needed; then the three inputs.
@@ -1942,7 +2069,8 @@ int nr_last_launch(const char* kernel, int* block_threads, int* flags) {
                              : strcmp(kernel, "k_raster_bwd") == 0 ? &g_last_bwd
                              : strcmp(kernel, "k_chamfer_nn") == 0 ? &g_last_chamfer
                              : strcmp(kernel, "k_point_face_nn") == 0 ? &g_last_point_mesh
-                             : strcmp(kernel, "k_face_point_nn") == 0 ? &g_last_face_point : nullptr;
+                             : strcmp(kernel, "k_face_point_nn") == 0 ? &g_last_face_point
+                             : strcmp(kernel, "k_icp_nn") == 0 ? &g_last_icp : nullptr;
     if (!slot) return fail(NR_ERR_ARGS, "nr_last_launch: unknown kernel name %s", kernel);
     const LaunchRec r = slot->load();
     if (!r.threads) return fail(NR_ERR_ARGS, "nr_last_launch: no %s launch recorded in this process", kernel);
